@@ -17,11 +17,17 @@ extract/count, scan, extract/scatter, [exchange], partition, group-by + cut + st
 overflow, chains; then statistics and reductions).  Inputs are uploaded before the timed region;
 outputs stay on the device.
 
-Secondary lines (same JSON object): "weak" = C2 (1M proteins per GPU; configs[1] at N=1) with its
-own roofline; at N=1 also the annotate leg (configs[3]: 10M queries vs the C2 DB in HBM) and the
-matrix-distance leg (configs[4]).
+A plain run does what the headline figure needs and no more: generate and upload the proteome,
+W warmup steps, exactly K timed steps, the result line.  --dump-outputs DIR then also writes what
+the last timed step computed (the kept set's hand-off, sampled) as DIR/<name>.npy.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]   (N>1 under torch.distributed.run)
+--full adds everything else (same JSON object): the untimed per-kernel diagnostic run, the
+hand-off + BDZ timing and the CPU baseline of the headline build; "weak" = C2 (1M proteins per GPU;
+configs[1] at N=1) with its own roofline; at N=1 also the recall leg, the annotate leg (configs[3]:
+10M queries vs the C2 DB in HBM), the two CLI legs and the matrix-distance leg (configs[4]).
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+        (N>1 under torch.distributed.run)
 """
 from __future__ import annotations
 
@@ -55,6 +61,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline steps: the per-kernel diagnostic run, the hand-off "
+                         "(--finish, --mph), the CPU baselines and the C2 / recall / annotate / CLI / matrix legs; "
+                         "the options of those legs take effect only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (a fixed output slice of the kept "
+                         "k-mers and their records, the per-function statistics, sampled signature flags) as "
+                         "DIR/<name>.npy; one GPU only")
     ap.add_argument("--seqs-total", type=int, default=50_000_000,
                     help="proteins of the headline proteome, split over the GPUs (strong scaling)")
     ap.add_argument("--families", type=int, default=4000)
@@ -89,7 +103,14 @@ def parse():
     ap.add_argument("--comm", choices=("rccl", "host"), default="rccl",
                     help="rank exchange of the build: RCCL over xGMI, or the gloo host transport (rehearses the "
                          "multi-rank path with several ranks on one GPU)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:  # a plain run: the headline build's steps only
+        a.weak_seqs = a.annot_queries = a.recall = a.matrix_seqs = a.cli_seqs = a.cli_queries = 0
+        a.finish = a.mph = 0
+        a.no_cpu_baseline = True
+    return a
 
 
 def host_cores() -> dict:
@@ -185,6 +206,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    if a.dump_outputs and world > 1:
+        sys.exit("--dump-outputs: the kept set's hand-off is a one-GPU call")
     dist = None
     cores = host_cores()
     workers = a.gen_workers or min(16, cores["usable"])
@@ -271,12 +294,16 @@ def main():
     b.prepare()
     prep_s = time.time() - t0
     log(f"C3 prepared in {prep_s:.1f} s")
-    head = _measure(skm, b, a.steps, a.warmup, c3, world, dist)
+    head = _measure(skm, b, a.steps, a.warmup, c3, world, dist, a.full)
     finish = None
+    if a.dump_outputs and not a.finish:
+        _dump_outputs(a.dump_outputs, b)
     if world == 1 and a.finish:  # the kept-set hand-off of the headline build (skm_build_finish)
         t = time.perf_counter()
         k = b.finish()
         dt = time.perf_counter() - t
+        if a.dump_outputs:
+            _dump_outputs(a.dump_outputs, b)
         c = b.counters()
         ok = len(k.keys) == c["kept"] and bool(np.all(k.keys[1:] > k.keys[:-1]))
         finish = {"seconds": dt, "kept": int(len(k.keys)), "bytes": 18 * int(len(k.keys)), "GBs": 18 * len(k.keys) / dt / 1e9,
@@ -305,6 +332,7 @@ def main():
         "value": head["value"],
         "unit": "k-mers/s",
         "n_gpus": world,
+        "full": bool(a.full),
         "steps": a.steps,
         "warmup": a.warmup,
         "ms_per_step": head["ms_per_step"],
@@ -359,7 +387,7 @@ def main():
             b.set_transport(skm.GlooTransport())
         b.prepare()
         prep2 = time.time() - t0
-        weak = _measure(skm, b, a.steps, a.warmup, c2, world, dist)
+        weak = _measure(skm, b, a.steps, a.warmup, c2, world, dist, a.full)
         out["weak"] = {"value": weak["value"], "unit": "k-mers/s", "ms_per_step": weak["ms_per_step"],
                        "scaling": "weak",
                        "config": {"workload": f"C2: {a.weak_seqs:,} proteins per GPU x {world}, k=8, signature build",
@@ -446,10 +474,47 @@ def _alg_bytes(kernel, c, res_bytes):
     return None if v is None or v <= 0 else float(v)
 
 
-def _measure(skm, b, steps, warmup, shard, world, dist):
-    """Warmup, then one untimed diagnostic run with every kernel launch bracketed by events (the
-    per-kernel GPU time that picks the dominant kernel), then exactly `steps` timed runs bracketed
-    by barriers, events around the dominant kernel's launches only; max over ranks."""
+DUMP_SEED = 20241115
+DUMP_KMERS = 1_000_000   # 8 + 4 + 20 bytes each in the files below
+DUMP_FLAGS = 1_000_000
+
+
+def _dump_outputs(out_dir, b):
+    """What a caller of the timed path receives after its last step, as float32 / float64 .npy
+    files, under 45 MB in all: the build's statistics (KeptKmers, include/skm.h skm_kept) whole,
+    and of the two large outputs a fixed sample.  Kept k-mers and their records: output slice 0
+    of 2^bits (skm_build_finish_slice: the k-mers whose fmix64(key) has its top bits 0, keys
+    ascending), with the fewest bits that bring the slice to about DUMP_KMERS k-mers or fewer -- a
+    function of the key alone, so two builds that keep the same set hand over the same rows.
+    Per-sequence signature flags: the sequences at seeded positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    kept = b.counters()["kept"]
+    bits = 0
+    while bits < 16 and (kept >> bits) > DUMP_KMERS:
+        bits += 1
+    k = b.finish_slice(bits, 0)
+    # a k-mer is 8 residue bytes in a u64: its two 32-bit halves are exact in float64
+    np.save(os.path.join(out_dir, "kept_keys_lo32_hi32.npy"),
+            np.stack([k.keys & np.uint64(0xFFFFFFFF), k.keys >> np.uint64(32)], axis=1).astype(np.float64))
+    np.save(os.path.join(out_dir, "kept_data.npy"),
+            np.stack([k.data[f] for f in ("avg_from_end", "function_index", "mean", "median", "var")],
+                     axis=1).astype(np.float32))
+    np.save(os.path.join(out_dir, "distinct_functions.npy"), k.distinct_functions.astype(np.float64))
+    np.save(os.path.join(out_dir, "seqs_with_func.npy"), k.seqs_with_func.astype(np.float64))
+    np.save(os.path.join(out_dir, "statistics.npy"),  # kept, seqs with a signature, distinct signatures, windows
+            np.array([kept, k.n_seqs_with_signature, k.distinct_signatures, k.n_windows], np.float64))
+    flags = b.signature_flags()
+    if len(flags) > DUMP_FLAGS:
+        flags = flags[np.sort(np.random.default_rng(DUMP_SEED).choice(len(flags), size=DUMP_FLAGS, replace=False))]
+    np.save(os.path.join(out_dir, "signature_flags.npy"), flags.astype(np.float32))
+    log(f"outputs of the last step written to {out_dir} (slice 0 of {1 << bits}: {len(k.keys):,} of {kept:,} kept "
+        f"k-mers)")
+
+
+def _measure(skm, b, steps, warmup, shard, world, dist, diagnostic=True):
+    """Warmup, then (diagnostic: --full) one untimed run with every kernel launch bracketed by
+    events (the per-kernel GPU time beside the roofline kernel's), then exactly `steps` timed runs
+    bracketed by barriers, events around the roofline kernel's launches only; max over ranks."""
     def barrier():
         if dist is not None:
             dist.barrier()
@@ -457,9 +522,11 @@ def _measure(skm, b, steps, warmup, shard, world, dist):
     for w in range(warmup):
         b.run()
         log(f"warmup {w + 1}/{warmup}")
-    b.set_kernel_timing(True)
-    b.run()
-    ktab = b.kernel_timings()
+    ktab = {}
+    if diagnostic:
+        b.set_kernel_timing(True)
+        b.run()
+        ktab = b.kernel_timings()
     # the roofline's kernel: the group-by (k_bucket_process), the dominant byte-moving kernel of the
     # main stream that carries the step's critical path; the kernel with the largest GPU time (the
     # background long-chain batches: latency-bound FP64 recurrences at a few waves per CU) is
@@ -467,8 +534,9 @@ def _measure(skm, b, steps, warmup, shard, world, dist):
     big = max(ktab, key=lambda k: ktab[k][0]) if ktab else None
     dom = "k_bucket_process"
     b.set_kernel_timing(True, dom)
-    log(f"roofline kernel: {dom} ({ktab.get(dom, (0, 0))[0]:.1f} ms in {ktab.get(dom, (0, 0))[1]} launches); "
-        f"largest GPU time: {big}")
+    if diagnostic:
+        log(f"roofline kernel: {dom} ({ktab.get(dom, (0, 0))[0]:.1f} ms in {ktab.get(dom, (0, 0))[1]} launches); "
+            f"largest GPU time: {big}")
     phase = {}
     dom_ms, dom_n = 0.0, 0
     barrier()

@@ -81,40 +81,41 @@ def _mutate_file(fam: Families, n: int, file_idx: int, seed: int, extras: bool):
     total = int(anc_len.sum())
     seq_start = np.zeros(n + 1, dtype=np.int64)
     seq_start[1:] = np.cumsum(anc_len)
-    within = np.arange(total, dtype=np.int64) - np.repeat(seq_start[:-1], anc_len)
-    src = np.repeat(fam.anc_off[:-1][fids], anc_len) + within
+    # ancestral site -> its residue in fam.anc (hypothetical members: fresh residues instead)
+    src = np.repeat(fam.anc_off[:-1][fids] - seq_start[:-1], anc_len)
+    src += np.arange(total, dtype=np.int64)
     hypo_pos = np.repeat(is_hypo, anc_len)
-    base = np.empty(total, dtype=np.uint8)
-    base[~hypo_pos] = fam.anc[src[~hypo_pos]]
-    base[hypo_pos] = _aa(rng, int(hypo_pos.sum()))
+    not_hypo = ~hypo_pos
+    base = fam.anc.take(src, mode="clip") if len(fam.anc) else np.empty(total, dtype=np.uint8)
+    base[hypo_pos] = _aa(rng, int(np.count_nonzero(hypo_pos)))
     # substitutions (ancestor-derived residues only)
-    sub = (rng.random(total) < 0.20) & ~hypo_pos
-    base[sub] = _aa(rng, int(sub.sum()))
+    u = np.empty(total)  # the per-site uniform draws, one buffer
+    sub = rng.random(out=u) < 0.20
+    sub &= not_hypo
+    sub_at = np.flatnonzero(sub)
+    base[sub_at] = _aa(rng, len(sub_at))
     # indels: each ancestral slot emits [residue unless deleted][insert if inserted]
-    keep = rng.random(total) >= 0.005
-    ins = (rng.random(total) < 0.005) & ~hypo_pos
+    deleted = np.flatnonzero(rng.random(out=u) < 0.005)
+    ins = rng.random(out=u) < 0.005
+    ins &= not_hypo
+    ins_at = np.flatnonzero(ins)
     star = rng.random(n) < 0.30
-    # slots: 2 per site, plus one '*' slot at the end of each sequence
-    slot_val = np.empty((total, 2), dtype=np.uint8)
-    slot_val[:, 0] = base
-    slot_val[:, 1] = 0
-    slot_val[ins, 1] = _aa(rng, int(ins.sum()))
-    slot_ok = np.stack([keep, ins], axis=1)
-    per_seq_sites = np.add.reduceat(keep.astype(np.int64) + ins, seq_start[:-1]) if total else np.zeros(n, np.int64)
-    per_seq_sites = np.where(anc_len > 0, per_seq_sites, 0)
+    ins_val = _aa(rng, len(ins_at))
+    # the few additions go into the kept residues in one np.insert: an inserted residue after its
+    # site (deleted or not), a '*' after its sequence's last site and that site's insert
+    kept = np.delete(base, deleted)
+    star_at = seq_start[1:][star]  # as a site index: the first site of the next sequence
+    add_key = np.concatenate([2 * ins_at + 1, 2 * star_at])
+    add_pos = np.concatenate([ins_at + 1 - np.searchsorted(deleted, ins_at, side="right"),
+                              star_at - np.searchsorted(deleted, star_at, side="left")])
+    add_val = np.concatenate([ins_val, np.full(len(star_at), ord("*"), dtype=np.uint8)])
+    order = np.argsort(add_key, kind="stable")
+    res = np.insert(kept, add_pos[order], add_val[order])
+    seq_of = lambda site: np.searchsorted(seq_start, site, side="right") - 1  # noqa: E731
+    per_seq_sites = anc_len - np.bincount(seq_of(deleted), minlength=n) + np.bincount(seq_of(ins_at), minlength=n)
     out_len = per_seq_sites + star.astype(np.int64)
-    flat_vals = slot_val.reshape(-1)[slot_ok.reshape(-1)]
-    # insert '*' after each starred sequence
-    res = np.empty(int(out_len.sum()), dtype=np.uint8)
     out_start = np.zeros(n + 1, dtype=np.int64)
     out_start[1:] = np.cumsum(out_len)
-    site_start = np.zeros(n + 1, dtype=np.int64)
-    site_start[1:] = np.cumsum(per_seq_sites)
-    dst_idx = np.arange(len(flat_vals), dtype=np.int64)
-    seq_of = np.repeat(np.arange(n), per_seq_sites)
-    dst_idx = dst_idx - site_start[seq_of] + out_start[seq_of]
-    res[dst_idx] = flat_vals
-    res[out_start[1:][star] - 1] = ord("*")
     # X sites (not on the trailing '*')
     xs = rng.random(len(res)) < 0.001
     xs[out_start[1:][star] - 1] = False

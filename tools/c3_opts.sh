@@ -10,7 +10,7 @@ i=0
 for set in "$@"; do
   args=""
   for kv in $set; do args="$args --option $kv"; done
-  timeout -k 10 300 python3 bench.py --cache-dir /tmp/c3 --steps 5 --warmup 1 --weak-seqs 0 --annot-queries 0 \
+  timeout -k 10 300 python3 bench.py --full --cache-dir /tmp/c3 --steps 5 --warmup 1 --weak-seqs 0 --annot-queries 0 \
     --matrix-seqs 0 --cli-seqs 0 --finish 0 --no-cpu-baseline $args --json-out $O/c3_opts_$i.json > $O/c3_opts_$i.log 2>&1 \
     || { tail -5 $O/c3_opts_$i.log; exit 1; }
   python3 -c "

@@ -28,7 +28,7 @@ case "$P" in legs*) ;; *) step cache 300 python3 bench.py --cache-dir /tmp/c3 --
 cd /tmp
 C3="python3 -u $R/bench.py --cache-dir /tmp/c3 --weak-seqs 0 --annot-queries 0 --matrix-seqs 0 --cli-seqs 0 --finish 0 --no-cpu-baseline"
 C2="python3 -u $R/tools/c3_diag.py --cache-dir /tmp/c3 --files 250"
-LEGS="python3 -u $R/bench.py --seqs-total 1000000 --cache-dir /tmp/legs --cli-seqs 0 --finish 0 --no-cpu-baseline"
+LEGS="python3 -u $R/bench.py --full --seqs-total 1000000 --cache-dir /tmp/legs --cli-seqs 0 --finish 0 --no-cpu-baseline"
 # PHASE: all | trace (stamps + C3/C2 traces) | pmc (C3/C2 counters) | legs (legs trace + counters)
 #        | legs_trace (the legs' kernel trace only) | sq (SQ counters of a C3 build)
 if [ "$P" = all ] || [ "$P" = trace ]; then
@@ -51,7 +51,7 @@ if [ "$P" = sq ]; then  # SQ counters of one C3 build (k_bucket_process at C3 si
 fi
 if [ "$P" = all ] || [ "$P" = legs ] || [ "$P" = legs_trace ]; then
   cd "$R"
-  step legs_cache 400 python3 -u $R/bench.py --seqs-total 1000000 --cache-dir /tmp/legs --cache-only
+  step legs_cache 400 python3 -u $R/bench.py --full --seqs-total 1000000 --cache-dir /tmp/legs --cache-only
   cd /tmp
   step prof_legs 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_legs" -o run -- $LEGS --steps 3 --warmup 1 --json-out "$O/bench_legs_trace.json"
   [ "$P" = legs_trace ] && { echo done; exit 0; }
