@@ -163,7 +163,11 @@ int skm_build_kernel_timings(skm_build* b, char* names, size_t names_cap, float*
  * [38] radix sort, [39] gather, [40] the D2H pieces; [41] the largest hand-off chunk (k-mers),
  * [42] 1 if the hand-off used 64-bit arena indices (>= 2^32 k-mers); [43] the kept arena's
  * capacity (k-mers); [44] device bytes free after prepare; [45] 1 if the passes alternate two
- * element buffers ("recs_rot"); returns entries written. */
+ * element buffers ("recs_rot"); [46] overflow sub-buckets whose light remainder (what is left once
+ * the heavy k-mers are split off, at most 2048 occurrences) was grouped by the LDS hash path
+ * (k_ovf_light) instead of the overflow sort, [47] the occurrences in them (both 0 with
+ * "ovf_light" 0; their kept k-mers count in [8], those of their groups of > 64 members in [10]);
+ * returns entries written. */
 int skm_build_counters(skm_build* b, uint64_t* out, int cap);
 /* Host transport: the rank collectives of a multi-process build run by the caller on host
  * buffers, for ranks joined by a channel other than RCCL (the tests drive it with
@@ -203,6 +207,9 @@ int skm_debug_transport_check(const skm_transport* tp, int rank, int world);
  *   "chain_prio", "bucket_prio", "chain_lds_kb", "host_timing",
  *   "heavy_min" (occurrences that send a k-mer to the heavy path), "split_min" (overflow
  *   sub-buckets at least this large are split into heavy keys + a light remainder),
+ *   "ovf_light" (1, the default: a light remainder of at most 2048 occurrences is grouped by the
+ *   LDS hash path of the group-by, k_ovf_light; 0: every remainder goes through the overflow
+ *   sort, as larger ones always do -- same results),
  *   "heavy_lsd" (1: every heavy k-mer through round 3's Boyer-Moore + LSD-sort path instead of
  *   the one-read bucketed path; it is the fallback for > 4096 functions or crowded buckets),
  *   "giant_class" (heavy chains of >= 2^class samples start right after the heavy kernel on

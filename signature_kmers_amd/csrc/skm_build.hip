@@ -777,6 +777,8 @@ enum : uint32_t {
     RUN_DEM_LJOBS = 11,     //   stashed jobs
     RUN_LONG_WANT = 12,     // stashed samples / jobs asked for by every pass (the fitted ones and
     RUN_LONG_WANTJ = 13,    //   the ones that did not fit: the demand of a redo)
+    RUN_ACC_LIGHT_SUB = 14, // run totals: light remainders grouped by k_ovf_light,
+    RUN_ACC_LIGHT_ELEMS = 15, //   and their elements
     RUN_ACC_NOVF = 16,      // run totals
     RUN_ACC_JOBS = 17,
     RUN_ACC_LENS = 18,
@@ -803,6 +805,7 @@ enum : uint32_t {
     PLAN_Q_SPLIT = 4,   // queue counters
     PLAN_Q_HEAVY = 5,
     PLAN_Q_REST = 6,
+    PLAN_Q_LIGHT = 7,   // k_ovf_light's queue over all NOVF entries
     PLAN_SLOTS = 8
 };
 
@@ -2567,6 +2570,7 @@ struct BucketArgs {
     unsigned long long* stamps;   // optional [32] per-phase cycle sums (diagnostics)
     uint64_t* big_desc;        // [big_cap][2] groups of > 64 members handed to k_big_groups
     uint32_t big_cap;
+    unsigned long long* big_ctr;  // descriptors reserved in big_desc (the pass's one counter, k_big_groups reads it)
     int prio;                  // wave issue priority of the group-by (above the concurrent chains)
     int pshift;                // KEY_BITS - pass bits (key_h43)
     int flag_check;            // 1: a signature flag is stored only when it reads 0 (option flag_check)
@@ -2809,8 +2813,9 @@ __device__ __forceinline__ void load_batch(const uint64_t* __restrict__ src_hi, 
 
 // One batch of n <= CAP elements.  (Measured: issuing the next batch's loads here, to overlap their
 // latency with this batch's work, gained nothing -- the other workgroup of the CU already hides
-// it -- and cost register spills.)
-__device__ __forceinline__ void process_sub(const uint64_t* __restrict__ src_hi, const uint64_t* __restrict__ src_lo,
+// it -- and cost register spills.)  Returns the kept k-mers the batch emitted (workgroup-uniform; those
+// of the groups handed to k_big_groups are not among them).
+__device__ __forceinline__ uint32_t process_sub(const uint64_t* __restrict__ src_hi, const uint64_t* __restrict__ src_lo,
                                             uint32_t n, const BucketArgs& A, uint64_t hprefix, const SubLds& L) {
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
     const uint32_t EMPTY = 0xFFFFFFFFu;
@@ -2930,7 +2935,7 @@ __device__ __forceinline__ void process_sub(const uint64_t* __restrict__ src_hi,
     // groups of more than 64 members go to k_big_groups: reserve their descriptors now, the
     // atomic's latency behind the class scatter
     unsigned long long big_base = 0;
-    if (tid == 0 && cstart[7] > cstart[6]) big_base = atomicAdd(&A.ctr[5], (unsigned long long)(cstart[7] - cstart[6]));
+    if (tid == 0 && cstart[7] > cstart[6]) big_base = atomicAdd(A.big_ctr, (unsigned long long)(cstart[7] - cstart[6]));
     __syncthreads();
     for (uint32_t g = tid; g < G; g += nt) {
         const uint32_t a = L.goff[L.glist[g]];
@@ -3062,40 +3067,53 @@ __device__ __forceinline__ void process_sub(const uint64_t* __restrict__ src_hi,
     }
     __syncthreads();
     SKM_STAMP(8);
+    return nkept;
+}
+
+// process_sub's LDS (~74 KB), shared by its two callers
+struct SubMem {
+    uint64_t hi[CAP];
+    uint64_t lo[CAP];
+    uint32_t tab[TAB];
+    __align__(16) uint16_t slot[CAP];
+    __align__(16) uint16_t rank[CAP];
+    __align__(16) uint16_t goff[CAP];
+    __align__(16) uint16_t glist[CAP];
+    __align__(16) uint16_t order[CAP];
+    __align__(16) uint16_t big[CAP / 2];
+    __align__(16) uint32_t wave[48];
+    uint32_t nbig;
+    uint64_t tlast;
+    uint32_t ccnt[24];
+};
+
+__device__ __forceinline__ SubLds sub_lds(SubMem& m) {
+    SubLds L;
+    L.ccnt = m.ccnt;
+    L.tlast = &m.tlast;
+    if (threadIdx.x == 0) m.tlast = __builtin_amdgcn_s_memtime();
+    L.hi = m.hi;
+    L.lo = m.lo;
+    L.tab = m.tab;
+    L.slot = m.slot;
+    L.rank = m.rank;
+    L.goff = m.goff;
+    L.glist = m.glist;
+    L.order = m.order;
+    L.big = m.big;
+    L.wave = m.wave;
+    L.nbig = &m.nbig;
+    L.lens32 = nullptr;
+    L.lens_sel = 0;
+    return L;
 }
 
 __global__ __launch_bounds__(BPK_THREADS, BPK_WAVES_EU) void k_bucket_process(BucketArgs A) {
     static_assert(CAP % BPK_THREADS == 0, "emit assigns CAP / BPK_THREADS elements per thread");
-    __shared__ uint64_t s_hi[CAP];
-    __shared__ uint64_t s_lo[CAP];
-    __shared__ uint32_t s_tab[TAB];
+    __shared__ SubMem s_mem;
     __shared__ uint32_t s_sub[(1 << MAX_B2) + 1];
-    __align__(16) __shared__ uint16_t s_slot[CAP];
-    __align__(16) __shared__ uint16_t s_rank[CAP];
-    __align__(16) __shared__ uint16_t s_goff[CAP];
-    __align__(16) __shared__ uint16_t s_glist[CAP];
-    __align__(16) __shared__ uint16_t s_order[CAP];
-    __align__(16) __shared__ uint16_t s_big[CAP / 2];
-    __shared__ __align__(16) uint32_t s_wave[48];
-    __shared__ uint32_t s_nbig;
-    __shared__ uint64_t s_tlast;
-    __shared__ uint32_t s_ccnt[24];
     if (A.skip && *A.skip) return;
-    SubLds L;
-    L.ccnt = s_ccnt;
-    L.tlast = &s_tlast;
-    if (threadIdx.x == 0) s_tlast = __builtin_amdgcn_s_memtime();
-    L.hi = s_hi;
-    L.lo = s_lo;
-    L.tab = s_tab;
-    L.slot = s_slot;
-    L.rank = s_rank;
-    L.goff = s_goff;
-    L.glist = s_glist;
-    L.order = s_order;
-    L.big = s_big;
-    L.wave = s_wave;
-    L.nbig = &s_nbig;
+    SubLds L = sub_lds(s_mem);
 
     const uint32_t bucket = blockIdx.x;
     if (bucket >= A.nbuckets) return;
@@ -3650,13 +3668,12 @@ __global__ __launch_bounds__(BP_THREADS) void k_overflow(BucketArgs A, OvfScratc
     // from the queue counter plan[q_slot] (largest first: the list is sorted by size class)
     const uint32_t q_lo = lo_slot < 0 ? 0u : plan[lo_slot], q_hi = plan[hi_slot];
     auto entry = [&](const OvfEntry e) {
-        if (e.n == 0) return;  // every key of the sub-bucket went to k_heavy
+        if (e.n == 0) return;  // every key of the sub-bucket went to k_heavy, or k_ovf_light took the rest
         if ((A.diag & 32) && e.n <= (uint32_t)CAP) return;  // diagnostics: the entries of one LDS chunk
         if ((A.diag & 64) && e.n > (uint32_t)CAP) return;   //   / of the global network, skipped
-        // src 2: the light remainder k_ovf_split compacted into this entry's own scratch (sorted in
-        // place: each chunk is loaded whole before it is written back)
-        const uint64_t* src_hi = (e.src == 2 ? S.hi : e.src ? A.tmp_hi : A.recs_hi) + e.off;
-        const uint64_t* src_lo = (e.src == 2 ? S.lo : e.src ? A.tmp_lo : A.recs_lo) + e.off;
+        // (after k_ovf_split: the light remainder, compacted to the front of the sub-bucket's range)
+        const uint64_t* src_hi = (e.src ? A.tmp_hi : A.recs_hi) + e.off;
+        const uint64_t* src_lo = (e.src ? A.tmp_lo : A.recs_lo) + e.off;
         uint64_t* ghi = S.hi + e.scratch;
         uint64_t* glo = S.lo + e.scratch;
         uint32_t* heads = S.heads + e.scratch;
@@ -3914,8 +3931,9 @@ __global__ __launch_bounds__(BP_THREADS) void k_overflow(BucketArgs A, OvfScratc
 // ordinal) with a one-workgroup global bitonic network costs O(n log^2 n) passes.  The large
 // sub-buckets are split first (k_ovf_split): an LDS table counts each key's occurrences, keys of
 // >= HEAVY_MIN occurrences are copied out to their own contiguous range (k_heavy), the rest (the
-// "light" keys, ~SUB_TARGET elements) is compacted in place of the sub-bucket's scratch and runs
-// through k_overflow as before, now mostly as a single LDS chunk.
+// "light" keys, ~SUB_TARGET elements) is compacted in place, to the front of the sub-bucket's range
+// in tmp.  A remainder of at most CAP elements is what process_sub was written for and is grouped
+// by k_ovf_light with the LDS hash path; a larger one runs through k_overflow as before.
 //
 // A heavy key needs no sort by (function, ordinal) (process_kmer_set, signature_build.tcc:219-293):
 //   - best function: a function with >= 80 % of the occurrences is the strict majority, so the
@@ -3934,6 +3952,9 @@ constexpr uint32_t SPLIT_TAB = 4096;        // LDS key table slots (load <= ~0.5
 constexpr uint32_t SPLIT_MAXH = 256;        // heavy keys taken out of one sub-bucket (more stay light)
 constexpr uint32_t HEAVY_WG = 512;
 constexpr uint32_t HEAVY_GRID = 1024;       // k_heavy: persistent workgroups taking keys from a queue
+// k_ovf_light's persistent grid: two of its workgroups fill a CU, as the group-by's do, so it stays
+// small (C3, one box, one run each: 64 -> 1308, 128 -> 1268-1306 over four runs, 256 -> 1267, 512 -> 1306 ms/step)
+constexpr uint32_t LIGHT_GRID = 128;
 
 struct HeavyKey {
     uint64_t off;       // first element in the heavy arrays
@@ -3983,7 +4004,7 @@ __device__ __forceinline__ uint32_t hr_seq(uint64_t x) { return (uint32_t)(x >> 
 constexpr uint32_t SPLIT_U = 8;   // elements per thread per iteration (loads issued together)
 
 // One workgroup per overflow entry of >= SPLIT_MIN elements (the first entries of the sorted list).
-__global__ __launch_bounds__(BP_THREADS) void k_ovf_split(BucketArgs A, OvfScratch S, HeavyArgs H, uint32_t heavy_min,
+__global__ __launch_bounds__(BP_THREADS) void k_ovf_split(BucketArgs A, HeavyArgs H, uint32_t heavy_min,
                                                            uint32_t* plan) {
     static_assert(SPLIT_TAB == 4096, "split_hash yields 12 bits");
     __shared__ uint32_t s_key[SPLIT_TAB];
@@ -4072,11 +4093,17 @@ __global__ __launch_bounds__(BP_THREADS) void k_ovf_split(BucketArgs A, OvfScrat
             }
         __syncthreads();
         if (s_heavy == 0) return;  // nothing heavy: unchanged
-        // ---- 3. scatter: heavy members to their key's range, the rest compacted into the scratch ----
-        uint64_t* lhi = S.hi + e.scratch;
-        uint64_t* llo = S.lo + e.scratch;
+        // ---- 3. scatter: heavy members to their key's range, the rest compacted in place, to the
+        //      front of the sub-bucket's own range.  An iteration's light members land below the
+        //      end of the elements it loaded (at most as many are light as were read so far), so
+        //      one barrier between its loads and its stores keeps a wave that runs ahead from
+        //      overwriting what a slower wave has yet to load: after it every wave holds the
+        //      iteration's elements in registers, and the next iteration's lie above every store ----
+        uint64_t* lhi = const_cast<uint64_t*>(src_hi);
+        uint64_t* llo = const_cast<uint64_t*>(src_lo);
         for (uint32_t j0 = 0; j0 < n; j0 += nt * SPLIT_U) {
             uint64_t eh[SPLIT_U], el[SPLIT_U];
+            uint32_t hids[SPLIT_U];
     #pragma unroll
             for (uint32_t u = 0; u < SPLIT_U; ++u) {
                 const uint32_t j = j0 + u * nt + tid;
@@ -4085,14 +4112,20 @@ __global__ __launch_bounds__(BP_THREADS) void k_ovf_split(BucketArgs A, OvfScrat
             }
     #pragma unroll
             for (uint32_t u = 0; u < SPLIT_U; ++u) {
-                const bool v = eh[u] != ~0ull;
-                uint32_t hid = 0xFFFFu;
-                if (v) {
+                hids[u] = 0xFFFFu;
+                if (eh[u] != ~0ull) {
                     const uint32_t rem = (uint32_t)(eh[u] >> 16) & REM_MASK;
                     uint32_t slot = split_hash(rem);
                     while (s_key[slot] != rem) slot = (slot + 1) & (SPLIT_TAB - 1);
-                    hid = s_hid[slot];
+                    hids[u] = s_hid[slot];
                 }
+                asm volatile("" : "+v"(el[u]));  // the load has returned before the barrier
+            }
+            __syncthreads();
+    #pragma unroll
+            for (uint32_t u = 0; u < SPLIT_U; ++u) {
+                const bool v = eh[u] != ~0ull;
+                const uint32_t hid = hids[u];
                 // light members: wave-aggregated cursor
                 const uint64_t lm = __ballot(v && hid == 0xFFFFu);
                 uint32_t lbase = 0;
@@ -4124,10 +4157,8 @@ __global__ __launch_bounds__(BP_THREADS) void k_ovf_split(BucketArgs A, OvfScrat
             }
         }
         __syncthreads();
-        if (tid == 0) {  // the entry now names its light remainder (in place in its scratch)
+        if (tid == 0) {  // the entry now names its light remainder (the front of its own range)
             e.n = n - s_heavy;
-            e.src = 2;
-            e.off = e.scratch;
             A.ovf[qe] = e;
         }
     };
@@ -4138,6 +4169,46 @@ __global__ __launch_bounds__(BP_THREADS) void k_ovf_split(BucketArgs A, OvfScrat
         if (q >= q_hi) break;
         entry(q);
         __syncthreads();
+    }
+}
+
+// The light remainders of at most CAP elements (k_ovf_split left them at the front of their
+// sub-bucket's range in tmp): one process_sub batch each, like a sub-bucket of k_bucket_process --
+// no sort, no scratch copy.  Persistent workgroups take the entries [0, plan[PLAN_NOVF]) from the
+// queue plan[PLAN_Q_LIGHT] and zero the count of each entry they group, so k_overflow (launched
+// after this kernel on both overflow streams) skips it.  A carries the overflow's job list and
+// counters; groups of more than 64 members go to the pass's one descriptor list (A.big_ctr).
+// stat: [0] remainders grouped, [1] their elements.
+__global__ __launch_bounds__(BPK_THREADS, BPK_WAVES_EU) void k_ovf_light(BucketArgs A, uint32_t* plan,
+                                                                         unsigned long long* stat) {
+    __shared__ SubMem s_mem;
+    __shared__ uint32_t s_q;
+    if (A.skip && *A.skip) return;
+    SubLds L = sub_lds(s_mem);
+    const uint32_t q_hi = plan[PLAN_NOVF];
+    unsigned long long kept = 0, nel = 0;
+    uint32_t nsub = 0;
+    for (;;) {
+        if (threadIdx.x == 0) s_q = atomicAdd(&plan[PLAN_Q_LIGHT], 1u);
+        __syncthreads();
+        const uint32_t q = s_q;
+        if (q >= q_hi) break;
+        const OvfEntry e = A.ovf[q];
+        if (e.n != 0 && e.n <= (uint32_t)CAP && e.src == 1) {
+            const uint64_t hprefix = (uint64_t)(A.bucket_base + e.bucket) << A.rem_bits;
+            L.lens_sel = (LENS_IN_TMP << LENS_SEL_SHIFT) | (2 * e.off);
+            L.lens32 = reinterpret_cast<uint32_t*>(A.tmp_hi + e.off);
+            kept += process_sub(A.tmp_hi + e.off, A.tmp_lo + e.off, e.n, A, hprefix, L);
+            if (threadIdx.x == 0) A.ovf[q].n = 0;
+            ++nsub;
+            nel += e.n;
+        }
+        __syncthreads();  // s_q is read by every thread before the next entry is taken
+    }
+    if (threadIdx.x == 0 && nsub) {
+        atomicAdd(&A.ctr[0], kept);  // the overflow's own kept count, as k_overflow keeps it
+        atomicAdd(&stat[0], (unsigned long long)nsub);
+        atomicAdd(&stat[1], nel);
     }
 }
 
@@ -4805,6 +4876,7 @@ __global__ __launch_bounds__(1024) void k_ovf_plan(PlanArgs P) {
         P.plan[PLAN_Q_SPLIT] = 0;
         P.plan[PLAN_Q_HEAVY] = 0;
         P.plan[PLAN_Q_REST] = 0;
+        P.plan[PLAN_Q_LIGHT] = 0;
         R[RUN_ACC_NOVF] += n;
         R[RUN_ACC_OVF_ELEMS] += s_elems;
         R[RUN_ACC_GROUPED] += nl;
@@ -4832,6 +4904,8 @@ __global__ void k_pass_account(const unsigned long long* __restrict__ ctr, unsig
     run[RUN_ACC_OVF_KEPT] += ctr[8];
     run[RUN_ACC_BIG] += ctr[5];
     run[RUN_ACC_BIG_KEPT] += ctr[6];
+    run[RUN_ACC_LIGHT_SUB] += ctr[21];
+    run[RUN_ACC_LIGHT_ELEMS] += ctr[22];
     run[RUN_LAST_JOBS] = j;
     if (ctr[3] > jobs_cap || ctr[8 + 3] > jobs2_cap || ctr[5] > big_cap || ctr[8 + 4] > lens_cap)
         atomicOr(&run[RUN_FLAGS], RUN_F_CAP);
@@ -5003,6 +5077,8 @@ struct Tune {
     int host_timing = 0;
     int heavy_min = (int)HEAVY_MIN;  // occurrences that make a key heavy (k_ovf_split)
     int split_min = (int)SPLIT_MIN;  // overflow sub-buckets of at least this size are split
+    int ovf_light = 1;               // 1: light remainders of <= CAP elements through k_ovf_light (the LDS
+                                     //   hash path); 0: every remainder through k_overflow's sort
     // heavy chains of >= 2^class samples start right after k_heavy on rotating chain streams
     // (0: off; -1, the default: 14 with one pass, off with key-range passes -- measured at C3, the
     // FP64-bound chains running beside the pass kernels slow them by more than the tail they
@@ -5114,7 +5190,7 @@ struct skm_build {
     hipEvent_t* ev_o = nullptr;
     hipEvent_t* ev_o3 = nullptr;
     float last_ms[15] = {};
-    uint64_t ovf_elems = 0, ovf_kept = 0;
+    uint64_t ovf_elems = 0, ovf_kept = 0, ovf_light_sub = 0, ovf_light_elems = 0;
 
     // host staging (reference emission order, only sequences with a kept function)
     // residues stream to HBM as batches arrive: packed (one 0 separator after each sequence) into
@@ -5201,7 +5277,7 @@ struct skm_build {
     hipEvent_t ev_scan = nullptr;       // tail_defer: the next pass's scan kernels are done
     bool rot = false;                   // recs_rot: odd passes split into d_recs_*2
     uint64_t free_after_prepare = 0;    // device bytes free after prepare (counters [44])
-    hipEvent_t ev_part = nullptr, ev_split = nullptr, ev_part_heavy = nullptr;
+    hipEvent_t ev_part = nullptr, ev_split = nullptr, ev_part_heavy = nullptr, ev_light = nullptr;
     DevBuf d_hv_keys, d_hv_rec, d_hv_len, d_hv_s0, d_hv_s1;   // heavy keys of the split overflow
     DevBuf d_sub_tab, d_jobs2, d_jobs3;
 
@@ -6622,6 +6698,7 @@ void phase_group(skm_build* b, uint32_t pass) {
     A.stamps = nullptr;
     A.big_desc = b->d_big_desc.as<uint64_t>();
     A.big_cap = (uint32_t)std::min<uint64_t>(b->big_cap, 0xFFFFFFFFull);
+    A.big_ctr = ctr_d + 5;
     A.skip = nullptr;
     A.sub_target = (uint32_t)std::max(0, b->tune.sub_target);
     A.diag = b->tune.diag;
@@ -6743,6 +6820,7 @@ void phase_group(skm_build* b, uint32_t pass) {
         H.gcap = giant_cap(b);
         H.gstat = b->d_gstat.as<unsigned long long>();
     }
+    const bool light = b->tune.ovf_light != 0;
     // issued before the group-by (concurrent with it), or after it (option serial_overflow: the
     // group-by's time alone)
     auto launch_overflow = [&]() {
@@ -6752,9 +6830,16 @@ void phase_group(skm_build* b, uint32_t pass) {
     SKM_HIP(hipEventRecord(b->ev_o[0], st2));
     SKM_HIP(hipEventRecord(b->ev_o3[0], st3));
     if (H.giant_min) SKM_HIP(hipMemsetAsync(b->gcount[pass].p, 0, 16, st2));
-    SKM_LAUNCH(b, k_ovf_split, dim3((uint32_t)std::max(1, b->tune.split_grid)), dim3(BP_THREADS), 0, st2, A2, S, H, key_min, plan_d);
+    SKM_LAUNCH(b, k_ovf_split, dim3((uint32_t)std::max(1, b->tune.split_grid)), dim3(BP_THREADS), 0, st2, A2, H, key_min, plan_d);
     SKM_HIP(hipEventRecord(b->ev_split, st2));
     SKM_HIP(hipStreamWaitEvent(st3, b->ev_split, 0));
+    // the light remainders of <= CAP elements on stream 3, beside k_heavy; both k_overflow launches
+    // read the entry list it edits, so stream 2's waits for it too (as does k_big_groups, below)
+    if (light) {
+        SKM_LAUNCH(b, k_ovf_light, dim3(LIGHT_GRID), dim3(BPK_THREADS), 0, st3, A3, plan_d,
+                   ctr_d + 21);
+        SKM_HIP(hipEventRecord(b->ev_light, st3));
+    }
     SKM_LAUNCH(b, k_heavy, dim3((uint32_t)std::max(1, b->tune.heavy_grid)), dim3(HEAVY_WG), 0, st2, A2, H);
     SKM_HIP(hipGetLastError());
     if (H.giant_min) {
@@ -6770,6 +6855,7 @@ void phase_group(skm_build* b, uint32_t pass) {
         SKM_HIP(hipEventRecord(b->gev_done[gs], b->gst[gs]));
         b->gused[gs] = true;
     }
+    if (light) SKM_HIP(hipStreamWaitEvent(st2, b->ev_light, 0));
     SKM_LAUNCH(b, k_overflow, dim3((uint32_t)std::max(1, b->tune.ovf_grid)), dim3(BP_THREADS), 0, st2, A2, S, plan_d, -1, (int)PLAN_NHEAVY,
                        (int)PLAN_Q_HEAVY, inline_min, prio);
     SKM_HIP(hipEventRecord(b->ev_o[1], st2));
@@ -6812,10 +6898,14 @@ void phase_group(skm_build* b, uint32_t pass) {
     }
     hipEvent_t* ev = b->ev;  // this pass's events (the deferred tail is issued after use_evset(pass + 1))
     auto big_tail = [=]() {
+    // k_ovf_light's groups of > 64 members are in the descriptor list too (in the default timeline
+    // it ends long before the group-by does)
+    if (light) SKM_HIP(hipStreamWaitEvent(tt, b->ev_light, 0));
     if (tail_async && b->tune.big_split) {
         // the two size classes of big groups are independent (disjoint descriptors and outputs):
         // the large class on a stream of its own, joined before the append
         SKM_HIP(hipStreamWaitEvent(b->stream_tail2, b->ev_tail_bp, 0));
+        if (light) SKM_HIP(hipStreamWaitEvent(b->stream_tail2, b->ev_light, 0));
         SKM_LAUNCH(b, k_big_groups<true>, dim3((uint32_t)std::max(1, b->tune.big_grid_large)), dim3(BIG_WG), 0,
                    b->stream_tail2, BA);
         SKM_HIP(hipEventRecord(b->ev_tail2, b->stream_tail2));
@@ -6833,8 +6923,9 @@ void phase_group(skm_build* b, uint32_t pass) {
     //      (the long ones on stream 2, the per-lane ones on stream 3), the group-by's on st ----
     SKM_HIP(hipEventRecord(b->ev_o3[0], st3));
     SKM_HIP(hipStreamWaitEvent(st2, b->ev_o3[0], 0));
-    launch_chains(b, st2, A2.jobs, ctr_d + 8 + 3, b->jobs2_cap, b->cs_ovf, A2.lens, nullptr, nullptr, nullptr,
-                  A.out_data, (uint32_t)b->tune.ovf_long_class, st3, b->ev_o3[2], (uint32_t)b->tune.ovf_chain_wgs);
+    // (k_ovf_light's jobs keep their lengths in tmp, like the group-by's)
+    launch_chains(b, st2, A2.jobs, ctr_d + 8 + 3, b->jobs2_cap, b->cs_ovf, A2.lens, reinterpret_cast<const uint32_t*>(A.recs_hi),
+                  reinterpret_cast<const uint32_t*>(A.tmp_hi), nullptr, A.out_data, (uint32_t)b->tune.ovf_long_class, st3, b->ev_o3[2], (uint32_t)b->tune.ovf_chain_wgs);
     SKM_HIP(hipEventRecord(b->ev_o[2], st2));
     SKM_HIP(hipEventRecord(b->ev_o3[1], st3));
     hipEvent_t* ev_o = b->ev_o;
@@ -7166,6 +7257,8 @@ void phase_final(skm_build* b) {
     b->ovf_kept = R[RUN_ACC_OVF_KEPT];
     b->n_big = R[RUN_ACC_BIG];
     b->big_kept = R[RUN_ACC_BIG_KEPT];
+    b->ovf_light_sub = R[RUN_ACC_LIGHT_SUB];
+    b->ovf_light_elems = R[RUN_ACC_LIGHT_ELEMS];
     b->n_local = R[RUN_ACC_GROUPED];
     b->ran = true;
 }
@@ -7320,6 +7413,7 @@ int skm_build_create(skm_build** out, const int* devices, int n_devices, const s
         SKM_HIP(hipEventCreateWithFlags(&b->st_ev[i], hipEventDisableTiming));
     }
     SKM_HIP(hipEventCreateWithFlags(&b->ev_split, hipEventDisableTiming));
+    SKM_HIP(hipEventCreateWithFlags(&b->ev_light, hipEventDisableTiming));
     set_geometry(b);
     *out = b;
     SKM_API_END
@@ -7659,6 +7753,7 @@ int skm_build_set_option(skm_build* b, const char* name, int64_t value) {
                : n == "host_timing" ? &t.host_timing
                : n == "heavy_min" ? &t.heavy_min
                : n == "split_min" ? &t.split_min
+               : n == "ovf_light" ? &t.ovf_light
                : n == "giant_class" ? &t.giant_class
                : n == "giant_passes" ? &t.giant_passes
                : n == "heavy_lsd" ? &t.heavy_lsd
@@ -7836,7 +7931,7 @@ int skm_debug_div_check(uint64_t nm, uint32_t per, uint64_t* mismatches) {
 int skm_build_counters(skm_build* b, uint64_t* out, int cap) {
     if (!b || !out) return SKM_E_ARG;
     auto us = [](double sec) { return (uint64_t)(sec * 1e6); };
-    const uint64_t v[46] = {b->n_windows, b->n_kept, b->n_overflow, b->n_jobs, b->n_lens, b->nseq, b->n_local,
+    const uint64_t v[48] = {b->n_windows, b->n_kept, b->n_overflow, b->n_jobs, b->n_lens, b->nseq, b->n_local,
                             b->ovf_elems, b->ovf_kept, b->n_big, b->big_kept, 1ull << b->pass_bits, b->valid_total,
                             b->giant_jobs, b->giant_max, b->n_redo, b->tot_cap, b->split_cap, b->long_cap,
                             b->long_jobs_cap, b->demand[0], b->demand[1], b->demand[2], b->demand[3],
@@ -7847,8 +7942,8 @@ int skm_build_counters(skm_build* b, uint64_t* out, int cap) {
                             (uint64_t)(1e3 * b->handoff.sort_ms), (uint64_t)(1e3 * b->handoff.gather_ms),
                             (uint64_t)(1e3 * b->handoff.d2h_ms), b->handoff.max_chunk,
                             (uint64_t)b->handoff.wide_index, b->kept_cap, b->free_after_prepare,
-                            (uint64_t)b->rot};
-    int n = std::min(cap, 46);
+                            (uint64_t)b->rot, b->ovf_light_sub, b->ovf_light_elems};
+    int n = std::min(cap, 48);
     for (int i = 0; i < n; ++i) out[i] = v[i];
     return n;
 }
@@ -8126,6 +8221,7 @@ void skm_build_destroy(skm_build* b) {
         if (b->st_ev[i]) (void)hipEventDestroy(b->st_ev[i]);
     }
     if (b->ev_split) (void)hipEventDestroy(b->ev_split);
+    if (b->ev_light) (void)hipEventDestroy(b->ev_light);
     if (b->ev_start) (void)hipEventDestroy(b->ev_start);
     for (int g = 0; g < skm_build::GSLOTS; ++g) {
         if (b->gst[g]) {
