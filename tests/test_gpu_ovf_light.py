@@ -3,7 +3,7 @@ sub-bucket's range) and k_ovf_light groups those of at most CAP = 2048 elements 
 path (process_sub); with option ovf_light = 0 they go through k_overflow's sort instead.
 
 Every input is built so that all its k-mers land in one level-2 sub-bucket: their 43-bit hashes
-(mix43 of the base-40 code, skm_common.h, restated here) share the top 23 bits, i.e. the level-1
+(mix43 of the base-40 code, skm_common.h, restated in planted.py) share the top 23 bits, i.e. the level-1
 bucket (12 bits) and every level-2 split of up to 11 bits.  Each occurrence has a protein of its
 own, X*a + 8-mer + X*b (exactly one valid window; length and offset vary), so the sub-bucket's size
 and every group's size are exact.  Results are compared bit for bit with the CPU oracle, with
@@ -12,137 +12,11 @@ import numpy as np
 import pytest
 
 import oracle_ref
+from planted import CAP, HEAVY_MIN, Planter, assert_same
 
 pytestmark = pytest.mark.gpu
 
-CAP = 2048
-HEAVY_MIN = 1024
-KEY_BITS = 43
-KEY_MASK = (1 << KEY_BITS) - 1
-MIX_M1, MIX_M2, MIX_SHIFT = 0x3C6EF372FE9, 0x5851F42D4C9, 22
-NCODES = 40 ** 8
-LETTERS = b"ACDEFGHIKLMNPQRSTVWY" + b"acdefghiklmnpqrstvwy"
 NF = 6
-
-
-def _inv_odd(m):
-    x = m
-    for _ in range(6):
-        x = (x * (2 - m * x)) & ((1 << 64) - 1)
-    return x & KEY_MASK
-
-
-MIX_I1, MIX_I2 = _inv_odd(MIX_M1), _inv_odd(MIX_M2)
-
-
-def mix43(k):
-    k = np.asarray(k, np.uint64)
-    x = (k * np.uint64(MIX_M1)) & np.uint64(KEY_MASK)
-    x = x ^ (x >> np.uint64(MIX_SHIFT))
-    x = (x * np.uint64(MIX_M2)) & np.uint64(KEY_MASK)
-    return x ^ (x >> np.uint64(MIX_SHIFT))
-
-
-def unmix43(x):
-    x = np.asarray(x, np.uint64)
-    x = x ^ (x >> np.uint64(MIX_SHIFT))
-    x = (x * np.uint64(MIX_I2)) & np.uint64(KEY_MASK)
-    x = x ^ (x >> np.uint64(MIX_SHIFT))
-    return (x * np.uint64(MIX_I1)) & np.uint64(KEY_MASK)
-
-
-def pack(seqs):
-    lens = np.array([len(s) for s in seqs], np.uint32)
-    off = np.zeros(len(seqs), np.uint64)
-    off[1:] = np.cumsum(lens[:-1])
-    return np.frombuffer(b"".join(seqs), np.uint8), off, lens
-
-
-def assert_same(got, ref):
-    np.testing.assert_array_equal(got.keys, ref["keys"])
-    for f in ("avg_from_end", "function_index", "mean", "median", "var"):
-        bad = np.nonzero(got.data[f] != ref["data"][f])[0]
-        assert len(bad) == 0, (f, len(bad), got.data[bad[:5]], ref["data"][bad[:5]],
-                               [int(k).to_bytes(8, "little") for k in got.keys[bad[:5]]])
-    np.testing.assert_array_equal(got.distinct_functions, ref["distinct_functions"])
-    np.testing.assert_array_equal(got.seqs_with_func, ref["seqs_with_func"])
-    assert got.n_seqs_with_signature == ref["n_seqs_with_signature"]
-    assert got.distinct_signatures == ref["distinct_signatures"]
-
-
-def kmer_of(code):
-    code = int(code)
-    out = bytearray(8)
-    for j in range(7, -1, -1):
-        code, d = divmod(code, 40)
-        out[j] = LETTERS[d]
-    return bytes(out)
-
-
-_codes = {}
-
-
-def bucket_codes():
-    """The valid codes of one sub-bucket: same top 23 hash bits as the code of b"MKVLAAGI"."""
-    if "c" not in _codes:
-        first = 0
-        for ch in b"MKVLAAGI":
-            first = first * 40 + LETTERS.index(ch)
-        top = int(mix43(np.array([first], np.uint64))[0]) >> 20
-        c = unmix43((np.uint64(top) << np.uint64(20)) | np.arange(1 << 20, dtype=np.uint64))
-        assert np.all(mix43(c) >> np.uint64(20) == np.uint64(top))
-        c = c[c < np.uint64(NCODES)]
-        c = c[c != np.uint64(first)]
-        np.random.default_rng(1234).shuffle(c)
-        _codes["c"] = (first, c)
-    return _codes["c"]
-
-
-class Planter:
-    """Occurrences of k-mers of the one sub-bucket, one protein each."""
-
-    def __init__(self, seed):
-        self.rng = np.random.default_rng(seed)
-        self.heavy_code, self.codes = bucket_codes()
-        self.next = 0
-        self.seqs, self.funcs, self.light = [], [], []
-
-    def code(self):
-        self.next += 1
-        return self.codes[self.next - 1]
-
-    def plant(self, code, funcs, light, long_at=None):
-        kmer = kmer_of(code)
-        for j, fn in enumerate(funcs):
-            a, b = int(self.rng.integers(0, 60)), int(self.rng.integers(0, 60))
-            if long_at is not None and j == long_at:
-                a, b = 40000, 30000  # a protein of more than 65535 residues
-            self.seqs.append(b"X" * a + kmer + b"X" * b)
-            self.funcs.append(fn)
-            self.light.append(light)
-        return kmer
-
-    def heavy(self, n, funcs=None, code=None):
-        return self.plant(self.heavy_code if code is None else code, funcs or [1] * n, False)
-
-    def group(self, funcs, long_at=None):
-        return self.plant(self.code(), list(funcs), True, long_at)
-
-    def singletons(self, n):
-        for _ in range(n):
-            self.group([int(self.rng.integers(0, NF))])
-
-    def arrays(self, order="shuffled"):
-        """order: the light members' sequences first, last, or shuffled among the heavy ones."""
-        n = len(self.seqs)
-        light = np.array(self.light, bool)
-        perm = self.rng.permutation(n)
-        if order == "first":
-            perm = np.concatenate([perm[light[perm]], perm[~light[perm]]])
-        elif order == "last":
-            perm = np.concatenate([perm[~light[perm]], perm[light[perm]]])
-        res, off, lens = pack([self.seqs[k] for k in perm])
-        return res, off, lens, np.array(self.funcs, np.uint16)[perm], np.arange(n, dtype=np.uint32)
 
 
 def contents(p):
