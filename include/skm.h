@@ -480,6 +480,35 @@ void skm_matrix_destroy(skm_matrix* m);
 /* Row band of rank `rank` of `world` GPUs with (nearly) equal triangle area. */
 int skm_matrix_tile_rows(uint32_t n_idx, int rank, int world, uint32_t* row_begin, uint32_t* row_end);
 
+/* Batched matrix distance: P independent problems (one family's sequences each) in one device
+ * pass.  Problem p owns the sequences [prob_seq[p], prob_seq[p+1]) and its own SeqIdMap index
+ * space [0, prob_nidx[p]); seq_idx[s] is local to the problem of s.  A k-mer that occurs in
+ * several problems pairs sequences only within each of them: every problem's pairs equal those
+ * of skm_matrix_* run on that problem alone.  The number of host synchronisations of a run does
+ * not depend on P. */
+typedef struct skm_matrix_batch skm_matrix_batch;
+typedef struct skm_matrix_batch_opts {
+    int32_t hypo_index;       /* as skm_matrix_opts                                               */
+    uint32_t small_cols;      /* 0 = built-in limit (1024); else min(small_cols, 1024): rows of
+                                 problems with more indices take the large-row kernel            */
+} skm_matrix_batch_opts;
+int skm_matrix_batch_create(skm_matrix_batch** out, skm_db* db, const uint8_t* residues, const uint64_t* seq_off,
+                            const uint32_t* seq_len, const uint32_t* seq_idx, const uint64_t* prob_seq,
+                            const uint32_t* prob_nidx, size_t n_prob);
+/* Reusable: a second run gives the same pairs. */
+int skm_matrix_batch_run(skm_matrix_batch* b, const skm_matrix_batch_opts* opts);
+/* Triples with problem-local indices, sorted by (problem, id1, id2); problem p's are
+ * [prob_off[p], prob_off[p+1]).  prob_off has P+1 entries.  Free with skm_pairs_free. */
+int skm_matrix_batch_pairs(skm_matrix_batch* b, skm_pairs* out, uint64_t* prob_off);
+/* [0]=windows [1]=hit records [2]=pair increments [3]=nonzero pairs [4]=groups (distinct
+ * (problem, k-mer)) [5]=rows (indices) on the small path [6]=rows on the large path */
+int skm_matrix_batch_counters(skm_matrix_batch* b, uint64_t* out, int cap);
+/* out[P]: groups of each problem of the last run -- its kmer_hit_map size (matrix_distance.h:110) */
+int skm_matrix_batch_group_counts(skm_matrix_batch* b, uint64_t* out);
+/* as skm_matrix_last_timings */
+int skm_matrix_batch_last_timings(skm_matrix_batch* b, float* ms, int cap);
+void skm_matrix_batch_destroy(skm_matrix_batch* b);
+
 /* find_best_call (call_functions.tcc:347-659) on the host.  function_index: nfunc C strings
  * (function.index column 1).  out_func receives the called function (NUL-terminated).      */
 int skm_find_best_call(const skm_kmer_call* calls, size_t ncalls, const char* const* function_index,

@@ -74,6 +74,10 @@ class _MatrixOpts(C.Structure):
                 ("max_tile_bytes", C.c_uint64)]
 
 
+class _MatrixBatchOpts(C.Structure):
+    _fields_ = [("hypo_index", C.c_int32), ("small_cols", C.c_uint32)]
+
+
 class _Pairs(C.Structure):
     _fields_ = [("pairs", C.POINTER(C.c_uint32)), ("n", C.c_uint64), ("n_hits", C.c_uint64)]
 
@@ -139,6 +143,13 @@ _SIGS = {
     "skm_matrix_pairs": (C.c_int, [_P, C.POINTER(_Pairs)]),
     "skm_pairs_free": (None, [C.POINTER(_Pairs)]),
     "skm_matrix_destroy": (None, [_P]),
+    "skm_matrix_batch_create": (C.c_int, [C.POINTER(_P), _P, _P, _P, _P, _P, _P, _P, C.c_size_t]),
+    "skm_matrix_batch_run": (C.c_int, [_P, C.POINTER(_MatrixBatchOpts)]),
+    "skm_matrix_batch_pairs": (C.c_int, [_P, C.POINTER(_Pairs), C.POINTER(C.c_uint64)]),
+    "skm_matrix_batch_counters": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
+    "skm_matrix_batch_group_counts": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "skm_matrix_batch_last_timings": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+    "skm_matrix_batch_destroy": (None, [_P]),
     "skm_matrix_tile_rows": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "skm_find_best_call": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_uint16),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_char_p, C.c_size_t]),
@@ -871,6 +882,104 @@ class MatrixDistance:
     def close(self):
         if self._h:
             lib().skm_matrix_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MatrixDistanceBatch:
+    """Many independent MatrixDistance problems in one device pass (skm_matrix_batch_*): what
+    kmers-matrix-distance-folder / -merge run per family.  Problem p owns the sequences
+    [prob_seq[p], prob_seq[p+1]) and its own SeqIdMap index space; seq_idx is local to each problem
+    (default: 0..n-1 within each) and prob_nidx its index count (default: max index + 1, or the
+    sequence count when seq_idx is None)."""
+
+    def __init__(self, db: CmphKmerDb, function_index, residues, seq_off, seq_len, prob_seq, seq_idx=None,
+                 prob_nidx=None):
+        self.db = db
+        fi = read_function_index(function_index) if isinstance(function_index, str) else list(function_index)
+        if "hypothetical protein" not in fi:  # call_functions.tcc:269-274 exits the process
+            raise SkmError("Cannot find hypothetical protein index")
+        self.hypo_index = fi.index("hypothetical protein")
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        prob_seq = np.ascontiguousarray(prob_seq, dtype=np.uint64)
+        self.n_prob = max(len(prob_seq) - 1, 0)
+        if len(prob_seq) == 0:
+            prob_seq = np.zeros(1, np.uint64)
+        ps = prob_seq.astype(np.int64)
+        if int(ps[-1]) != len(seq_len) or (len(ps) > 1 and np.any(np.diff(ps) < 0)) or int(ps[0]) != 0:
+            raise SkmError("prob_seq must rise from 0 to the number of sequences")
+        cnt = np.diff(ps)
+        if seq_idx is None:
+            seq_idx = np.arange(len(seq_len), dtype=np.int64) - np.repeat(ps[:-1], cnt)
+            if prob_nidx is None:
+                prob_nidx = cnt
+        seq_idx = np.ascontiguousarray(seq_idx, dtype=np.uint32)
+        if prob_nidx is None:
+            prob_nidx = np.zeros(self.n_prob, np.int64)
+            if len(seq_idx):
+                np.maximum.at(prob_nidx, np.repeat(np.arange(self.n_prob), cnt), seq_idx.astype(np.int64) + 1)
+        prob_nidx = np.ascontiguousarray(prob_nidx, dtype=np.uint32)
+        if len(prob_nidx) != self.n_prob:
+            raise SkmError("prob_nidx must have one entry per problem")
+        self.prob_nidx = prob_nidx
+        self._h = C.c_void_p()
+        _check(lib().skm_matrix_batch_create(C.byref(self._h), db._h, _ptr(residues), _ptr(seq_off), _ptr(seq_len),
+                                             _ptr(seq_idx), _ptr(prob_seq), _ptr(prob_nidx), self.n_prob))
+
+    def run(self, small_cols: int = 0):
+        opts = _MatrixBatchOpts(self.hypo_index, small_cols)
+        _check(lib().skm_matrix_batch_run(self._h, C.byref(opts)))
+
+    def timings(self) -> dict:
+        ms = (C.c_float * 5)()
+        n = lib().skm_matrix_batch_last_timings(self._h, ms, 5)
+        return dict(zip(["hits", "group", "pairs", "emit", "total"], list(ms)[:n]))
+
+    def counters(self) -> dict:
+        v = (C.c_uint64 * 7)()
+        n = lib().skm_matrix_batch_counters(self._h, v, 7)
+        return dict(zip(["windows", "hits", "increments", "pairs", "groups", "rows_small", "rows_large"],
+                        [int(x) for x in list(v)[:n]]))
+
+    def group_counts(self) -> np.ndarray:
+        """Distinct hit k-mers of each problem (its kmer_hit_map size, matrix_distance.h:110)."""
+        v = (C.c_uint64 * max(self.n_prob, 1))()
+        _check(lib().skm_matrix_batch_group_counts(self._h, v))
+        return np.array(list(v)[:self.n_prob], np.uint64)
+
+    def pairs_flat(self):
+        """((n, 3) u32 triples of every problem back to back, prob_off[P+1])."""
+        out = _Pairs()
+        off = (C.c_uint64 * (self.n_prob + 1))()
+        _check(lib().skm_matrix_batch_pairs(self._h, C.byref(out), off))
+        try:
+            n = int(out.n)
+            flat = (np.ctypeslib.as_array(out.pairs, shape=(n * 3,)).reshape(n, 3).copy() if n
+                    else np.zeros((0, 3), np.uint32))
+            return flat, np.array(list(off), np.uint64)
+        finally:
+            lib().skm_pairs_free(C.byref(out))
+
+    def pairs(self) -> list:
+        """One (n, 3) u32 (id1, id2, count) array per problem, indices local to the problem, id1 < id2,
+        sorted by (id1, id2)."""
+        flat, off = self.pairs_flat()
+        return [flat[int(off[p]):int(off[p + 1])] for p in range(self.n_prob)]
+
+    def compute(self, small_cols: int = 0) -> list:
+        self.run(small_cols)
+        return self.pairs()
+
+    def close(self):
+        if self._h:
+            lib().skm_matrix_batch_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

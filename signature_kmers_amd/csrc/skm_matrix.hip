@@ -32,6 +32,16 @@
 // the group has pairs in -- the suffix of members from the band's first row on (k_md_route_*,
 // one all-to-all) -- and each GPU counts the pairs of its band from the groups it received.  The
 // host concatenates the bands in row order.
+//
+// Batch (skm_matrix_batch_*): P independent problems in one pass.  Problem p's indices are numbered
+// base[p] + local (base = exclusive scan of the problems' index counts), the whole batch goes
+// through k_md_hits / k_md_slot / the radix sort once, and a group also starts where the problem
+// of the index changes (k_md_starts_seg), so a k-mer never pairs sequences of two problems.
+//   k_md_rows_seg  rows of problems with <= SEG_COLS indices: one wave per row, four waves per
+//                  workgroup, a u32 LDS histogram per wave over the row's columns up to the end of
+//                  its problem; nonzero columns compacted 64 at a time by ballot
+//   k_md_rows      rows of larger problems, with the row's column end taken from its problem
+//   k_md_gather_seg  triples with problem-local indices; k_md_proboff reads prob_off from the row scan
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -287,6 +297,12 @@ struct MdRowArgs {
     uint32_t* scratch;         // per row, from ubo[row]: (id2, count) pairs
     unsigned int* rowctr;      // work queue
     unsigned long long* incs;  // pair increments (diagnostics / roofline)
+    // batch (null / 0 on the single-problem path): the queue runs over rowsel[0..nsel) and a
+    // row's columns end with its problem, at pbase[idx_prob[row] + 1]
+    const uint32_t* rowsel = nullptr;
+    uint32_t nsel = 0;
+    const uint32_t* idx_prob = nullptr;  // [nidx] problem of each global index
+    const uint32_t* pbase = nullptr;     // [P+1] first global index of each problem
 };
 
 __device__ __forceinline__ bool md_entry(const MdRowArgs& R, uint64_t e, uint32_t& row, uint64_t& ge) {
@@ -369,15 +385,15 @@ __global__ __launch_bounds__(MR_THREADS) void k_md_rows(MdRowArgs R) {
         __syncthreads();
         if (tid == 0) s_row = atomicAdd(R.rowctr, 1u);
         __syncthreads();
-        const uint32_t row = s_row;
-        if (row >= R.rows) break;
+        if (s_row >= (R.rowsel ? R.nsel : R.rows)) break;
+        const uint32_t row = R.rowsel ? R.rowsel[s_row] : s_row;
         const uint64_t l0 = R.rowoff[row], l1 = R.rowoff[row + 1];
         if (l0 == l1) {
             if (tid == 0) R.rownnz[row] = 0;
             continue;
         }
         const uint64_t id1 = (uint64_t)R.r0 + row;
-        const uint64_t ncol = R.nidx - id1 - 1;
+        const uint64_t ncol = (R.idx_prob ? (uint64_t)R.pbase[R.idx_prob[id1] + 1] : R.nidx) - id1 - 1;
         const bool wide = l1 - l0 > 65535u;
         const uint32_t cpp = wide ? MR_WORDS : 2u * MR_WORDS;
         const bool multi = ncol > cpp;
@@ -505,6 +521,136 @@ __global__ void k_md_gather(const uint32_t* __restrict__ scratch, const uint64_t
     }
 }
 
+// ---- batch of problems (skm_matrix_batch_*) ----
+// group starts of a batch: the slot or the problem of the index differs from the previous
+// composite (within a slot the composites are sorted by global index, so by problem)
+__global__ void k_md_starts_seg(const uint64_t* __restrict__ c, uint64_t n, uint32_t idx_bits, uint64_t idx_mask,
+                                const uint32_t* __restrict__ idx_prob, uint32_t* __restrict__ flag) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    bool start = true;
+    if (e > 0) {
+        const uint64_t a = c[e - 1], b = c[e];
+        start = (a >> idx_bits) != (b >> idx_bits) || idx_prob[a & idx_mask] != idx_prob[b & idx_mask];
+    }
+    flag[e] = start ? 1u : 0u;
+}
+
+// Rows of small problems (<= SEG_COLS indices): one wave per row, rows taken SEG_RB at a time from
+// the queue over rowsel.  The wave's u32 LDS histogram covers the row's columns id1+1 .. end of its
+// problem (< SEG_COLS of them) and is all-zero between rows.  The row's entries are loaded 64 at a
+// time (one per lane) and handed to groups of SEG_SUB lanes, which stride over the entry's
+// partners comp[e+1 .. group end); LDS atomics add the counts.  The nonzero columns are compacted
+// in column order, 64 per step, by ballot + popcount into the row's scratch range, and reset.
+// LDS operations of one wave execute in order, so the wave needs no barrier between the phases
+// (the wavefront fences only pin the compiler's order).
+constexpr uint32_t SEG_COLS = 1024;
+constexpr int SEG_WAVES = 4, SEG_THREADS = SEG_WAVES * 64;
+constexpr uint32_t SEG_SUB = 16, SEG_RB = 4;
+
+__global__ __launch_bounds__(SEG_THREADS) void k_md_rows_seg(MdRowArgs R) {
+    __shared__ uint32_t hs[SEG_WAVES][SEG_COLS];
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t* h = hs[threadIdx.x >> 6];
+    for (uint32_t c = lane; c < SEG_COLS; c += 64) h[c] = 0;
+    const uint32_t sub = lane / SEG_SUB, sl = lane % SEG_SUB;
+    const uint64_t lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+    uint64_t incs = 0;
+    for (;;) {
+        uint32_t q0 = 0;
+        if (lane == 0) q0 = atomicAdd(R.rowctr, SEG_RB);
+        q0 = __shfl(q0, 0, 64);
+        if (q0 >= R.nsel) break;
+        const uint32_t q1 = min(q0 + SEG_RB, R.nsel);
+        for (uint32_t qi = q0; qi < q1; ++qi) {
+            const uint32_t row = R.rowsel[qi];
+            const uint64_t l0 = R.rowoff[row], l1 = R.rowoff[row + 1];
+            if (l0 == l1) {
+                if (lane == 0) R.rownnz[row] = 0;
+                continue;
+            }
+            const uint64_t clo = (uint64_t)row + 1;
+            const uint32_t ncol = min((uint32_t)(R.pbase[R.idx_prob[row] + 1] - clo), SEG_COLS);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            for (uint64_t kb = l0; kb < l1; kb += 64) {
+                const uint64_t k = kb + lane;
+                uint64_t qa = 0, qb = 0;
+                if (k < l1) {
+                    const uint64_t e = R.rowlist[k];
+                    qa = e + 1;
+                    qb = R.segstart[R.S[e + 1]];
+                }
+                const uint32_t ne = (uint32_t)min<uint64_t>(64, l1 - kb);
+                for (uint32_t i0 = 0; i0 < ne; i0 += 64 / SEG_SUB) {  // wave-uniform: every lane shuffles
+                    const uint32_t i = (i0 + sub) & 63u;
+                    const uint64_t a = __shfl(qa, i, 64), b = __shfl(qb, i, 64);  // lanes past ne hold 0, 0
+                    for (uint64_t q = a + sl; q < b; q += SEG_SUB) {
+                        const uint64_t cq = R.comp[q], cp = R.comp[q - 1];
+                        if (cq == cp) continue;  // duplicate (kmer, index)
+                        const uint32_t c = (uint32_t)((cq & R.idx_mask) - clo);
+                        if (c < ncol) atomicAdd(&h[c], 1u);
+                        ++incs;
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            uint32_t* out = R.scratch + 2 * R.ubo[row];
+            uint32_t nnz = 0;
+            for (uint32_t cb = 0; cb < ncol; cb += 64) {
+                const uint32_t c = cb + lane;
+                const uint32_t v = c < ncol ? h[c] : 0u;
+                const uint64_t m = __ballot(v != 0);
+                if (v) {
+                    const uint32_t o = nnz + (uint32_t)__popcll(m & lt);
+                    out[2 * o] = (uint32_t)(clo + c);
+                    out[2 * o + 1] = v;
+                    h[c] = 0;
+                }
+                nnz += (uint32_t)__popcll(m);
+            }
+            if (lane == 0) R.rownnz[row] = nnz;
+        }
+    }
+    uint64_t x = incs;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+    if (lane == 0 && x) atomicAdd(R.incs, (unsigned long long)x);
+}
+
+// rows in order, one wave per row: (id2, count) scratch pairs with global indices -> triples with
+// the indices local to the row's problem
+__global__ void k_md_gather_seg(const uint32_t* __restrict__ scratch, const uint64_t* __restrict__ ubo,
+                                const uint64_t* __restrict__ fo, const uint32_t* __restrict__ idx_prob,
+                                const uint32_t* __restrict__ pbase, uint32_t rows, uint32_t* __restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u, wpb = blockDim.x >> 6;
+    for (uint32_t row = blockIdx.x * wpb + (threadIdx.x >> 6); row < rows; row += gridDim.x * wpb) {
+        const uint64_t a = fo[row], cnt = fo[row + 1] - a;
+        if (!cnt) continue;
+        const uint32_t b0 = pbase[idx_prob[row]];
+        const uint32_t* src = scratch + 2 * ubo[row];
+        for (uint64_t j = lane; j < cnt; j += 64) {
+            out[3 * (a + j)] = row - b0;
+            out[3 * (a + j) + 1] = src[2 * j] - b0;
+            out[3 * (a + j) + 2] = src[2 * j + 1];
+        }
+    }
+}
+
+// prob_off[p] = pairs before problem p = the row scan at the problem's first row
+__global__ void k_md_proboff(const uint64_t* __restrict__ fo, const uint32_t* __restrict__ pbase, uint32_t np1,
+                             uint64_t* __restrict__ po) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < np1) po[p] = fo[pbase[p]];
+}
+
+// groups per problem (each problem's kmer_hit_map size): one count per group start
+__global__ void k_md_probgroups(const uint32_t* __restrict__ flag, const uint64_t* __restrict__ c, uint64_t n,
+                                uint64_t idx_mask, const uint32_t* __restrict__ idx_prob,
+                                unsigned long long* __restrict__ pg) {
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (uint64_t)gridDim.x * blockDim.x)
+        if (flag[e]) atomicAdd(&pg[idx_prob[c[e] & idx_mask]], 1ull);
+}
+
 // ---- multi-GPU: hits to the k-mer's owner, groups to the row bands they touch ----
 __device__ __forceinline__ uint32_t md_owner(uint64_t k, uint32_t W) {
     return (uint32_t)(((xmix(k) >> 32) * (uint64_t)W) >> 32);
@@ -623,6 +769,18 @@ struct skm_matrix {
     uint32_t band_lo = 0, band_hi = 0;
 };
 
+// P problems over one skm_matrix whose index space is the concatenation of the problems'
+struct skm_matrix_batch {
+    skm_matrix* M = nullptr;          // queries with global indices, nidx = pbase[P]
+    uint32_t P = 0;
+    std::vector<uint32_t> pbase;      // [P+1]
+    DevBuf d_iprob, d_pbase, d_sel, d_poff;
+    uint32_t sel_cols = 0;            // small_cols of the row selection in d_sel (0: none yet)
+    uint32_t n_small = 0, n_large = 0;
+    std::vector<uint64_t> prob_off;   // [P+1] of the last run
+    bool ran = false;
+};
+
 namespace {
 
 // ---- rank collectives of the multi-GPU matrix (host transport or RCCL) ----
@@ -737,12 +895,17 @@ uint64_t md_group(skm_matrix* M, const unsigned long long* keys, const uint32_t*
 }
 
 // group boundaries of the sorted composites d_comp[0..n): S (scan of group starts), segstart
-uint64_t md_bounds(skm_matrix* M, uint64_t n, uint32_t idx_bits, hipStream_t st) {
+// (idx_prob: a batch's problem per index -- a group also ends where the problem changes)
+uint64_t md_bounds(skm_matrix* M, uint64_t n, uint32_t idx_bits, hipStream_t st, const uint32_t* idx_prob = nullptr) {
     if (!n) return 0;
     M->d_flag.ensure(4 * n);
     M->d_S.ensure(8 * (n + 1));
-    hipLaunchKernelGGL(k_md_starts, dim3((uint32_t)ceil_div(n, 256)), dim3(256), 0, st, M->d_comp.as<uint64_t>(), n,
-                       idx_bits, M->d_flag.as<uint32_t>());
+    if (idx_prob)
+        hipLaunchKernelGGL(k_md_starts_seg, dim3((uint32_t)ceil_div(n, 256)), dim3(256), 0, st, M->d_comp.as<uint64_t>(),
+                           n, idx_bits, (1ull << idx_bits) - 1, idx_prob, M->d_flag.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(k_md_starts, dim3((uint32_t)ceil_div(n, 256)), dim3(256), 0, st, M->d_comp.as<uint64_t>(), n,
+                           idx_bits, M->d_flag.as<uint32_t>());
     M->scan.run(M->d_flag.as<uint32_t>(), n, M->d_S.as<uint64_t>(), st);
     M->d_seg.ensure(8 * (n + 1));
     hipLaunchKernelGGL(k_md_segstart, dim3((uint32_t)ceil_div(n, 256)), dim3(256), 0, st, M->d_flag.as<uint32_t>(),
@@ -870,14 +1033,9 @@ uint64_t md_exchange(skm_matrix* M, uint64_t n_local, uint32_t idx_bits, hipStre
     return n_band;
 }
 
-void matrix_run(skm_matrix* M, const skm_matrix_opts* o) {
+// k_md_hits over the handle's resident queries: (kmer, index) records in d_rkey / d_ridx, count in d_nrec
+void md_hits(skm_matrix* M, int32_t hypo_index, hipStream_t st) {
     skm_db* db = M->db;
-    SKM_HIP(hipSetDevice(db->device));
-    hipStream_t st = M->stream;
-    const uint32_t r0_in = (o->row_begin == 0 && o->row_end == 0) ? 0u : o->row_begin;
-    const uint32_t r1_in = (o->row_begin == 0 && o->row_end == 0) ? M->nidx : std::min(o->row_end, M->nidx);
-    SKM_HIP(hipEventRecord(M->ev[0], st));
-    // 1. hits
     SKM_HIP(hipMemsetAsync(M->d_nrec.p, 0, 16, st));
     if (M->rp && db->m) {
         MdHitArgs A;
@@ -888,7 +1046,7 @@ void matrix_run(skm_matrix* M, const skm_matrix_opts* o) {
         A.seq_idx = M->d_idx.as<uint32_t>();
         A.D = db->dev;
         A.exact = db->exact ? 1 : 0;
-        A.hypo = o->hypo_index >= 0 ? (uint32_t)o->hypo_index : 0xFFFFFFFFu;
+        A.hypo = hypo_index >= 0 ? (uint32_t)hypo_index : 0xFFFFFFFFu;
         A.rec_key = M->d_rkey.as<unsigned long long>();
         A.rec_idx = M->d_ridx.as<uint32_t>();
         A.nrec = M->d_nrec.as<unsigned long long>();
@@ -897,6 +1055,17 @@ void matrix_run(skm_matrix* M, const skm_matrix_opts* o) {
         hipLaunchKernelGGL(k_md_hits, dim3(grid), dim3(MD_THREADS), 0, st, A);
         SKM_HIP(hipGetLastError());
     }
+}
+
+void matrix_run(skm_matrix* M, const skm_matrix_opts* o) {
+    skm_db* db = M->db;
+    SKM_HIP(hipSetDevice(db->device));
+    hipStream_t st = M->stream;
+    const uint32_t r0_in = (o->row_begin == 0 && o->row_end == 0) ? 0u : o->row_begin;
+    const uint32_t r1_in = (o->row_begin == 0 && o->row_end == 0) ? M->nidx : std::min(o->row_end, M->nidx);
+    SKM_HIP(hipEventRecord(M->ev[0], st));
+    // 1. hits
+    md_hits(M, o->hypo_index, st);
     SKM_HIP(hipEventRecord(M->ev[1], st));
     uint64_t n = 0;
     SKM_HIP(hipMemcpyAsync(&n, M->d_nrec.p, 8, hipMemcpyDeviceToHost, st));
@@ -1006,6 +1175,155 @@ void matrix_run(skm_matrix* M, const skm_matrix_opts* o) {
     M->last_ms[3] = emit_ms - pairs_ms;                                // row lists + compaction
     SKM_HIP(hipEventElapsedTime(&M->last_ms[4], M->ev[0], M->ev[3]));  // total
     M->ran = true;
+}
+
+// The whole batch in one pass over the global index space.  Host synchronisations: hit count,
+// group count, row-list totals, prob_off (with the pair total), end -- none depends on P.
+void batch_run(skm_matrix_batch* B, const skm_matrix_batch_opts* o) {
+    skm_matrix* M = B->M;
+    SKM_HIP(hipSetDevice(M->db->device));
+    hipStream_t st = M->stream;
+    const uint32_t P = B->P, rows = M->nidx;
+    const uint32_t small = o->small_cols ? std::min(o->small_cols, SEG_COLS) : SEG_COLS;
+    if (small != B->sel_cols && rows) {  // rows of small problems first, then the rows of large ones
+        std::vector<uint32_t> sel(rows);
+        uint32_t ns = 0;
+        for (uint32_t p = 0; p < P; ++p)
+            if (B->pbase[p + 1] - B->pbase[p] <= small)
+                for (uint32_t i = B->pbase[p]; i < B->pbase[p + 1]; ++i) sel[ns++] = i;
+        uint32_t nl = ns;
+        for (uint32_t p = 0; p < P; ++p)
+            if (B->pbase[p + 1] - B->pbase[p] > small)
+                for (uint32_t i = B->pbase[p]; i < B->pbase[p + 1]; ++i) sel[nl++] = i;
+        B->d_sel.ensure(4ull * rows);
+        SKM_HIP(hipMemcpy(B->d_sel.p, sel.data(), 4ull * rows, hipMemcpyHostToDevice));
+        B->n_small = ns;
+        B->n_large = rows - ns;
+        B->sel_cols = small;
+    }
+    SKM_HIP(hipEventRecord(M->ev[0], st));
+    md_hits(M, o->hypo_index, st);
+    SKM_HIP(hipEventRecord(M->ev[1], st));
+    uint64_t n = 0;
+    SKM_HIP(hipMemcpyAsync(&n, M->d_nrec.p, 8, hipMemcpyDeviceToHost, st));
+    SKM_HIP(hipStreamSynchronize(st));
+    M->n_hits = n;
+    M->n_local_hits = n;
+    M->n_incs = 0;
+    M->n_pairs = 0;
+    M->n_groups = 0;
+    B->prob_off.assign((size_t)P + 1, 0);
+    const uint32_t idx_bits = (uint32_t)std::max(1, ilog2_ceil(std::max<uint64_t>(rows, 2)));
+    const uint32_t* iprob = B->d_iprob.as<uint32_t>();
+    const uint32_t* pbase = B->d_pbase.as<uint32_t>();
+    if (n) {
+        md_group(M, M->d_rkey.as<unsigned long long>(), M->d_ridx.as<uint32_t>(), M->d_nrec.as<unsigned long long>(), n,
+                 idx_bits, st);
+        M->n_groups = md_bounds(M, n, idx_bits, st, iprob);
+    }
+    SKM_HIP(hipEventRecord(M->ev[2], st));
+    float pairs_ms = 0, emit_ms = 0;
+    uint64_t out_n = 0;
+    if (n && rows) {
+        M->d_rlen.ensure(4ull * rows);
+        M->d_rub.ensure(4ull * rows);
+        M->d_rcur.ensure(4ull * rows);
+        M->d_roff.ensure(8ull * (rows + 1));
+        M->d_ubo.ensure(8ull * (rows + 1));
+        M->d_rnnz.ensure(4ull * rows);
+        M->d_fo.ensure(8ull * (rows + 1));
+        M->d_incs.ensure(16);
+        B->d_poff.ensure(8ull * (P + 1));
+        SKM_HIP(hipMemsetAsync(M->d_rlen.p, 0, 4ull * rows, st));
+        SKM_HIP(hipMemsetAsync(M->d_rub.p, 0, 4ull * rows, st));
+        SKM_HIP(hipMemsetAsync(M->d_rcur.p, 0, 4ull * rows, st));
+        SKM_HIP(hipMemsetAsync(M->d_incs.p, 0, 16, st));
+        MdRowArgs R;
+        R.comp = M->d_comp.as<uint64_t>();
+        R.S = M->d_S.as<uint64_t>();
+        R.segstart = M->d_seg.as<uint64_t>();
+        R.n = n;
+        R.idx_mask = (1ull << idx_bits) - 1;
+        R.r0 = 0;
+        R.rows = rows;
+        R.nidx = rows;
+        R.rowlen = M->d_rlen.as<uint32_t>();
+        R.rowub = M->d_rub.as<uint32_t>();
+        R.cursor = M->d_rcur.as<uint32_t>();
+        R.rowoff = M->d_roff.as<uint64_t>();
+        R.ubo = M->d_ubo.as<uint64_t>();
+        R.rownnz = M->d_rnnz.as<uint32_t>();
+        R.incs = M->d_incs.as<unsigned long long>();
+        R.idx_prob = iprob;
+        R.pbase = pbase;
+        const uint32_t ge = (uint32_t)std::min<uint64_t>(ceil_div(n, 256), 256ull * 32);
+        hipLaunchKernelGGL(k_md_rowstat, dim3(ge), dim3(256), 0, st, R);
+        M->scan.run(R.rowlen, rows, M->d_roff.as<uint64_t>(), st);
+        M->scan.run(R.rowub, rows, M->d_ubo.as<uint64_t>(), st);
+        uint64_t tot[2] = {0, 0};
+        SKM_HIP(hipMemcpyAsync(&tot[0], M->d_roff.as<uint64_t>() + rows, 8, hipMemcpyDeviceToHost, st));
+        SKM_HIP(hipMemcpyAsync(&tot[1], M->d_ubo.as<uint64_t>() + rows, 8, hipMemcpyDeviceToHost, st));
+        SKM_HIP(hipStreamSynchronize(st));
+        M->d_rlist.ensure(4 * std::max<uint64_t>(tot[0], 1));
+        M->d_scr.ensure(8 * std::max<uint64_t>(tot[1], 1));
+        R.rowlist = M->d_rlist.as<uint32_t>();
+        R.scratch = M->d_scr.as<uint32_t>();
+        hipLaunchKernelGGL(k_md_rowfill, dim3(ge), dim3(256), 0, st, R);
+        SKM_HIP(hipGetLastError());
+        hipEvent_t e0 = M->ev[4], e1 = M->ev[5];
+        SKM_HIP(hipEventRecord(e0, st));
+        int dev = 0, ncu = 256;
+        SKM_HIP(hipGetDevice(&dev));
+        SKM_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+        ncu = std::max(1, ncu);
+        unsigned int* ctr = reinterpret_cast<unsigned int*>(M->d_incs.as<unsigned long long>() + 1);
+        if (B->n_small) {  // 16 KB of LDS and 4 waves per workgroup: 8 workgroups fill a CU's 32 wave slots
+            MdRowArgs Rs = R;
+            Rs.rowsel = B->d_sel.as<uint32_t>();
+            Rs.nsel = B->n_small;
+            Rs.rowctr = ctr;
+            const uint64_t want = ceil_div(B->n_small, (uint64_t)SEG_WAVES * SEG_RB);
+            hipLaunchKernelGGL(k_md_rows_seg, dim3((uint32_t)std::min<uint64_t>(want, 8ull * ncu)), dim3(SEG_THREADS), 0, st, Rs);
+            SKM_HIP(hipGetLastError());
+        }
+        if (B->n_large) {
+            MdRowArgs Rl = R;
+            Rl.rowsel = B->d_sel.as<uint32_t>() + B->n_small;
+            Rl.nsel = B->n_large;
+            Rl.rowctr = ctr + 1;
+            hipLaunchKernelGGL(k_md_rows, dim3((uint32_t)std::min<uint32_t>(B->n_large, (uint32_t)ncu)), dim3(MR_THREADS), 0, st, Rl);
+            SKM_HIP(hipGetLastError());
+        }
+        SKM_HIP(hipEventRecord(e1, st));
+        M->scan.run(R.rownnz, rows, M->d_fo.as<uint64_t>(), st);
+        hipLaunchKernelGGL(k_md_proboff, dim3((uint32_t)ceil_div((uint64_t)P + 1, 256)), dim3(256), 0, st,
+                           M->d_fo.as<uint64_t>(), pbase, P + 1, B->d_poff.as<uint64_t>());
+        SKM_HIP(hipGetLastError());
+        SKM_HIP(hipMemcpyAsync(B->prob_off.data(), B->d_poff.p, 8ull * (P + 1), hipMemcpyDeviceToHost, st));
+        SKM_HIP(hipStreamSynchronize(st));
+        out_n = B->prob_off[P];
+        M->d_out.ensure(12 * std::max<uint64_t>(out_n, 1));
+        hipLaunchKernelGGL(k_md_gather_seg, dim3((uint32_t)std::min<uint64_t>(ceil_div(rows, 4), 256ull * 16)), dim3(256), 0,
+                           st, M->d_scr.as<uint32_t>(), M->d_ubo.as<uint64_t>(), M->d_fo.as<uint64_t>(), iprob, pbase, rows,
+                           M->d_out.as<uint32_t>());
+        SKM_HIP(hipGetLastError());
+        SKM_HIP(hipEventRecord(M->ev[3], st));
+        SKM_HIP(hipEventSynchronize(M->ev[3]));
+        SKM_HIP(hipEventElapsedTime(&pairs_ms, e0, e1));
+        unsigned long long incs = 0;
+        SKM_HIP(hipMemcpy(&incs, M->d_incs.p, 8, hipMemcpyDeviceToHost));
+        M->n_incs = incs;
+    }
+    SKM_HIP(hipEventRecord(M->ev[3], st));
+    SKM_HIP(hipEventSynchronize(M->ev[3]));
+    M->n_pairs = out_n;
+    SKM_HIP(hipEventElapsedTime(&M->last_ms[0], M->ev[0], M->ev[1]));  // hits
+    SKM_HIP(hipEventElapsedTime(&M->last_ms[1], M->ev[1], M->ev[2]));  // group (slot + sort + bounds)
+    M->last_ms[2] = pairs_ms;                                          // pair increments (both row kernels)
+    SKM_HIP(hipEventElapsedTime(&emit_ms, M->ev[2], M->ev[3]));
+    M->last_ms[3] = emit_ms - pairs_ms;                                // row lists + compaction
+    SKM_HIP(hipEventElapsedTime(&M->last_ms[4], M->ev[0], M->ev[3]));  // total
+    B->ran = true;
 }
 
 }  // namespace
@@ -1156,6 +1474,123 @@ void skm_pairs_free(skm_pairs* p) {
     if (!p) return;
     std::free(p->pairs);
     std::memset(p, 0, sizeof(*p));
+}
+
+int skm_matrix_batch_create(skm_matrix_batch** out, skm_db* db, const uint8_t* residues, const uint64_t* seq_off,
+                            const uint32_t* seq_len, const uint32_t* seq_idx, const uint64_t* prob_seq,
+                            const uint32_t* prob_nidx, size_t n_prob) {
+    SKM_API_BEGIN
+    SKM_CHECK(out && db, SKM_E_ARG, "null argument");
+    SKM_CHECK(n_prob == 0 || (prob_seq && prob_nidx), SKM_E_ARG, "null array");
+    SKM_CHECK(n_prob < 0xFFFFFFFFull, SKM_E_ARG, "too many problems in one batch");
+    const uint64_t n_seqs = n_prob ? prob_seq[n_prob] : 0;
+    SKM_CHECK(n_prob == 0 || prob_seq[0] == 0, SKM_E_ARG, "prob_seq must start at 0");
+    for (size_t p = 0; p < n_prob; ++p)
+        SKM_CHECK(prob_seq[p] <= prob_seq[p + 1], SKM_E_ARG, "prob_seq is not monotone");
+    SKM_CHECK(n_seqs == 0 || (residues && seq_off && seq_len && seq_idx), SKM_E_ARG, "null array");
+    SKM_CHECK(n_seqs < 0xFFFFFFFFull, SKM_E_ARG, "too many sequences in one batch");
+    std::vector<uint32_t> pbase(n_prob + 1, 0);
+    uint64_t total = 0;
+    for (size_t p = 0; p < n_prob; ++p) {
+        total += prob_nidx[p];
+        SKM_CHECK(total < 0xFFFFFFFFull, SKM_E_ARG, "too many sequence indices in one batch");
+        pbase[p + 1] = (uint32_t)total;
+    }
+    std::vector<uint32_t> gidx(n_seqs), iprob(total);
+    for (size_t p = 0; p < n_prob; ++p) {
+        for (uint64_t s = prob_seq[p]; s < prob_seq[p + 1]; ++s) {
+            SKM_CHECK(seq_idx[s] < prob_nidx[p], SKM_E_ARG, "seq_idx out of range");
+            gidx[s] = pbase[p] + seq_idx[s];
+        }
+        std::fill(iprob.begin() + pbase[p], iprob.begin() + pbase[p + 1], (uint32_t)p);
+    }
+    auto* B = new skm_matrix_batch();
+    try {
+        const int rc = skm_matrix_create(&B->M, db, residues, seq_off, seq_len, gidx.data(), (size_t)n_seqs, (uint32_t)total);
+        if (rc) throw Error(rc, skm_last_error());
+        B->P = (uint32_t)n_prob;
+        B->pbase = pbase;
+        B->prob_off.assign(n_prob + 1, 0);
+        B->d_iprob.ensure(4 * std::max<uint64_t>(total, 1));
+        B->d_pbase.ensure(4 * (n_prob + 1));
+        if (total) SKM_HIP(hipMemcpy(B->d_iprob.p, iprob.data(), 4 * total, hipMemcpyHostToDevice));
+        SKM_HIP(hipMemcpy(B->d_pbase.p, pbase.data(), 4 * (n_prob + 1), hipMemcpyHostToDevice));
+    } catch (...) {
+        skm_matrix_batch_destroy(B);
+        throw;
+    }
+    *out = B;
+    SKM_API_END
+}
+
+int skm_matrix_batch_run(skm_matrix_batch* b, const skm_matrix_batch_opts* opts) {
+    SKM_API_BEGIN
+    SKM_CHECK(b && opts, SKM_E_ARG, "null argument");
+    batch_run(b, opts);
+    SKM_API_END
+}
+
+int skm_matrix_batch_pairs(skm_matrix_batch* b, skm_pairs* out, uint64_t* prob_off) {
+    SKM_API_BEGIN
+    SKM_CHECK(b && out && prob_off, SKM_E_ARG, "null argument");
+    SKM_CHECK(b->ran, SKM_E_STATE, "skm_matrix_batch_run has not been called");
+    skm_matrix* m = b->M;
+    SKM_HIP(hipSetDevice(m->db->device));
+    std::memset(out, 0, sizeof(*out));
+    out->n = m->n_pairs;
+    out->n_hits = m->n_hits;
+    out->pairs = (uint32_t*)std::malloc(12 * std::max<uint64_t>(m->n_pairs, 1));
+    SKM_CHECK(out->pairs, SKM_E_OOM, "host allocation failed");
+    if (m->n_pairs) SKM_HIP(hipMemcpy(out->pairs, m->d_out.p, 12 * m->n_pairs, hipMemcpyDeviceToHost));
+    std::memcpy(prob_off, b->prob_off.data(), 8 * ((size_t)b->P + 1));
+    SKM_API_END
+}
+
+int skm_matrix_batch_counters(skm_matrix_batch* b, uint64_t* out, int cap) {
+    if (!b || !out) return SKM_E_ARG;
+    const skm_matrix* m = b->M;
+    const uint64_t v[7] = {m->n_windows, m->n_hits, m->n_incs, m->n_pairs, m->n_groups, b->n_small, b->n_large};
+    const int n = std::min(cap, 7);
+    for (int i = 0; i < n; ++i) out[i] = v[i];
+    return n;
+}
+
+int skm_matrix_batch_group_counts(skm_matrix_batch* b, uint64_t* out) {
+    SKM_API_BEGIN
+    SKM_CHECK(b && (out || b->P == 0), SKM_E_ARG, "null argument");
+    SKM_CHECK(b->ran, SKM_E_STATE, "skm_matrix_batch_run has not been called");
+    skm_matrix* m = b->M;
+    std::fill(out, out + b->P, 0ull);
+    const uint64_t n = m->n_hits;
+    if (n && b->P) {  // the sorted composites and their group-start flags of the last run are still resident
+        SKM_HIP(hipSetDevice(m->db->device));
+        b->d_poff.ensure(8ull * (b->P + 1));
+        SKM_HIP(hipMemsetAsync(b->d_poff.p, 0, 8ull * b->P, m->stream));
+        const uint32_t idx_bits = (uint32_t)std::max(1, ilog2_ceil(std::max<uint64_t>(m->nidx, 2)));
+        hipLaunchKernelGGL(k_md_probgroups, dim3((uint32_t)std::min<uint64_t>(ceil_div(n, 256), 256ull * 32)), dim3(256), 0,
+                           m->stream, m->d_flag.as<uint32_t>(), m->d_comp.as<uint64_t>(), n, (1ull << idx_bits) - 1,
+                           b->d_iprob.as<uint32_t>(), b->d_poff.as<unsigned long long>());
+        SKM_HIP(hipGetLastError());
+        SKM_HIP(hipMemcpyAsync(out, b->d_poff.p, 8ull * b->P, hipMemcpyDeviceToHost, m->stream));
+        SKM_HIP(hipStreamSynchronize(m->stream));
+    }
+    SKM_API_END
+}
+
+int skm_matrix_batch_last_timings(skm_matrix_batch* b, float* ms, int cap) {
+    if (!b) return SKM_E_ARG;
+    return skm_matrix_last_timings(b->M, ms, cap);
+}
+
+void skm_matrix_batch_destroy(skm_matrix_batch* b) {
+    if (!b) return;
+    if (b->M) {
+        (void)hipSetDevice(b->M->db->device);
+        if (b->M->stream) (void)hipStreamSynchronize(b->M->stream);
+    }
+    skm_matrix* m = b->M;
+    delete b;  // its device buffers first, on the handle's device
+    skm_matrix_destroy(m);
 }
 
 void skm_matrix_destroy(skm_matrix* m) {
