@@ -61,6 +61,8 @@ typedef struct skm_kmer_call {
 const char* skm_last_error(void);
 const char* skm_version(void);
 int skm_device_count(int* n);
+/* hipMemGetInfo of a device: the bytes free for allocation right now, and the device's total */
+int skm_device_mem_info(int device, uint64_t* free_bytes, uint64_t* total_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Signature build.  Replaces SignatureBuilder<K>::extract_kmers + process_kmers
@@ -336,6 +338,51 @@ int skm_db_open_mem(skm_db** out, const uint8_t* mph, size_t mph_len, const uint
  * HBM as an open-addressing table (load <= 1/2) + the 10-byte records.  skm_db_lookup returns
  * the record index, or n for a miss.                                                          */
 int skm_db_open_kept(skm_db** out, const uint64_t* keys, const skm_stored_kmer_data* data, size_t n, int device);
+
+/* The same exact-key DB made on the device from a finished build, without a host copy of the kept
+ * set.  Its table is range-reduced: any number of 16-byte slots (key, record index, function_index
+ * << 16 | mean), not a power of two and possibly more than 2^32; a key's home slot is the high 64
+ * bits of fmix64(key) * slots, and probing is linear with a wrap at the table's end. */
+typedef struct skm_kept_db_opts {
+    uint32_t load_pct;      /* 0 = 40; else 10..95: slots = max(16, ceil(100 n / load_pct)).  The
+                               recall lookup at load 0.6 measured 31-41 % slower than on the host
+                               path's table, at 0.5 5-16 % slower, at 0.4 8-13 % faster
+                                                                           */
+    int32_t  release_work;  /* 1: free the build handle's per-pass work buffers first (below)   */
+    uint64_t slots;         /* 0 = from load_pct; else exactly this many slots (> n); tests and
+                               callers that size the table themselves                           */
+} skm_kept_db_opts;
+
+/* Exact-key DB (KeptKmerDB, kept_kmer_db.h:20-27) over the kept k-mers of b's last run, built on
+ * b's device from the resident arena: no host copy of keys or records. opts NULL = defaults.
+ * Runs the build first if it has not run since prepare (as skm_build_finish does).  world_size > 1
+ * returns SKM_E_STATE (the kept set is sharded over the ranks).  At most 2^32 - 2 kept k-mers.
+ * The DB is independent of b: it holds the table only -- not the 10-byte records, so
+ * skm_matrix_create / skm_matrix_batch_create over it return SKM_E_ARG -- and skm_db_lookup returns
+ * a k-mer's index in b's arena (a permutation of 0..n-1 over the members; n for a miss).  When the
+ * table cannot be allocated the call returns SKM_E_OOM with the bytes asked for and the bytes free
+ * in skm_last_error(), and b stays usable.
+ * release_work = 1 frees every device buffer of b except the kept arena, the statistics and the
+ * signature flags before the table is allocated (and whether or not that allocation succeeds):
+ * skm_build_finish, _finish_slice, _signature_flags and _counters return what they returned before,
+ * and every call that would need the freed buffers -- skm_build_add_batch, _reserve, _prepare,
+ * _run, _group_run, and a finish after skm_build_set_option -- returns SKM_E_STATE.  Such a handle
+ * is only read out and destroyed. */
+int skm_build_kept_db(skm_build* b, const skm_kept_db_opts* opts, skm_db** out);
+
+/* host only: the table skm_build_kept_db would allocate for n keys */
+int skm_kept_db_plan(uint64_t n, const skm_kept_db_opts* opts, uint64_t* slots, uint64_t* bytes);
+/* host only (test hook): the home slot of key in a table of `slots` slots -- the same function the
+ * device uses */
+int skm_debug_kept_slot(uint64_t key, uint64_t slots, uint64_t* slot);
+/* batched record word of a key as the call path reads it: function_index << 16 | mean, or
+ * 0xFFFFFFFF for a miss (BDZ DBs: whatever record the search lands on, as fetch does). Any DB. */
+int skm_db_lookup_fm(skm_db* db, const uint64_t* keys, size_t n, uint32_t* fm_out);
+/* out[0]=slots [1]=table bytes [2]=keys [3]=longest probe sequence seen at insert (slots examined
+ * by one key, 1 = every key sits in its home slot; 0 for a table made by skm_db_open_kept, which
+ * does not record it) [4]=1 if range-reduced (made by skm_build_kept_db); 0s for a BDZ DB;
+ * returns entries written */
+int skm_db_table_info(skm_db* db, uint64_t* out, int cap);
 /* cmph_size() (cmph_kmer.h:102); for an exact DB the number of kept k-mers */
 int skm_db_size(skm_db* db, uint32_t* m);
 /* Batched cmph_search(hash, key, 8) (cmph_kmer.h:90-92); idx >= size is a miss. */

@@ -18,7 +18,7 @@ __all__ = [
     "SkmError", "lib", "K", "UNDEFINED_FUNCTION", "STORED_DTYPE", "CALL_DTYPE",
     "SignatureBuilder", "KeptKmers", "CmphKmerDb", "FunctionCaller", "mph_build",
     "kmer_to_str", "str_to_kmer", "keys_from_strings", "device_count", "MatrixDistance", "SeqIdMap",
-    "matrix_tile_rows",
+    "matrix_tile_rows", "KeptKmerDb", "DeviceKeptKmerDb", "kept_db_plan", "kept_slot",
 ]
 
 K = 8
@@ -78,6 +78,10 @@ class _MatrixBatchOpts(C.Structure):
     _fields_ = [("hypo_index", C.c_int32), ("small_cols", C.c_uint32)]
 
 
+class _KeptDbOpts(C.Structure):
+    _fields_ = [("load_pct", C.c_uint32), ("release_work", C.c_int32), ("slots", C.c_uint64)]
+
+
 class _Pairs(C.Structure):
     _fields_ = [("pairs", C.POINTER(C.c_uint32)), ("n", C.c_uint64), ("n_hits", C.c_uint64)]
 
@@ -87,6 +91,7 @@ _SIGS = {
     "skm_last_error": (C.c_char_p, []),
     "skm_version": (C.c_char_p, []),
     "skm_device_count": (C.c_int, [C.POINTER(C.c_int)]),
+    "skm_device_mem_info": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "skm_build_create": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.POINTER(_BuildOpts)]),
     "skm_build_add_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t]),
     "skm_build_prepare": (C.c_int, [_P]),
@@ -118,6 +123,11 @@ _SIGS = {
     "skm_db_open": (C.c_int, [C.POINTER(_P), C.c_char_p, C.c_char_p, C.c_int]),
     "skm_db_open_mem": (C.c_int, [C.POINTER(_P), _P, C.c_size_t, _P, C.c_size_t, C.c_int]),
     "skm_db_open_kept": (C.c_int, [C.POINTER(_P), _P, _P, C.c_size_t, C.c_int]),
+    "skm_build_kept_db": (C.c_int, [_P, C.POINTER(_KeptDbOpts), C.POINTER(_P)]),
+    "skm_kept_db_plan": (C.c_int, [C.c_uint64, C.POINTER(_KeptDbOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "skm_debug_kept_slot": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "skm_db_lookup_fm": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "skm_db_table_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     "skm_db_size": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "skm_db_lookup": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "skm_debug_db_lookup_generic": (C.c_int, [_P, _P, C.c_size_t, _P]),
@@ -209,6 +219,13 @@ def device_count() -> int:
     return n.value
 
 
+def device_mem_info(device: int = 0) -> tuple:
+    """(free, total) bytes of a device's memory (hipMemGetInfo)."""
+    fr, tot = C.c_uint64(), C.c_uint64()
+    _check(lib().skm_device_mem_info(device, C.byref(fr), C.byref(tot)))
+    return fr.value, tot.value
+
+
 def warm_device(device: int = 0) -> None:
     """Bring up the process's HIP runtime and the device context (one throwaway build handle), so
     that a timed one-shot build does not include the runtime's start-up."""
@@ -278,6 +295,7 @@ class SignatureBuilder:
         dev = (C.c_int * 1)(device)
         _check(lib().skm_build_create(C.byref(self._h), dev, 1, C.byref(opts)))
         self.n_functions = n_functions
+        self.device = device
 
     def add_batch(self, residues, seq_off, seq_len, seq_func, seq_id=None):
         residues = np.ascontiguousarray(residues, dtype=np.uint8)
@@ -395,6 +413,17 @@ class SignatureBuilder:
         out = np.zeros(max(n, 1), np.uint8)
         _check(lib().skm_build_signature_flags(self._h, _ptr(out), n))
         return out[:n]
+
+    def kept_db(self, load_pct: int = 0, slots: int = 0, release_work: bool = False) -> "DeviceKeptKmerDb":
+        """skm_build_kept_db: the exact-key DB (KeptKmerDB<8>) over the kept k-mers of the last run,
+        built on the device from the resident arena -- no host copy of the kept set.  load_pct /
+        slots size its range-reduced table (kept_db_plan); release_work frees the handle's per-pass
+        work buffers first, after which the handle can only be read out (finish, finish_slice,
+        signature_flags, counters) and closed: run / prepare / add_batch raise SkmError."""
+        opts = _KeptDbOpts(int(load_pct), 1 if release_work else 0, int(slots))
+        h = C.c_void_p()
+        _check(lib().skm_build_kept_db(self._h, C.byref(opts), C.byref(h)))
+        return DeviceKeptKmerDb(h, self.device)
 
     @staticmethod
     def _kept(k) -> KeptKmers:
@@ -604,6 +633,24 @@ class CmphKmerDb:
             _check(lib().skm_debug_db_lookup_generic(self._h, _ptr(keys), len(keys), _ptr(out)))
         return out
 
+    def lookup_fm(self, keys: np.ndarray) -> np.ndarray:
+        """skm_db_lookup_fm: per key the record word the call path reads, function_index << 16 |
+        mean, or 0xFFFFFFFF for a miss (a BDZ DB: whatever record the search lands on, as fetch)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros(len(keys), dtype=np.uint32)
+        if len(keys):
+            _check(lib().skm_db_lookup_fm(self._h, _ptr(keys), len(keys), _ptr(out)))
+        return out
+
+    def table_info(self) -> tuple:
+        """skm_db_table_info: (slots, table bytes, keys, longest probe sequence seen at insert, 1 if
+        range-reduced); zeros for a BDZ DB."""
+        v = (C.c_uint64 * 5)()
+        n = lib().skm_db_table_info(self._h, v, 5)
+        if n < 0:
+            _check(n)
+        return tuple(int(x) for x in v)
+
     def close(self):
         if self._h:
             lib().skm_db_close(self._h)
@@ -627,6 +674,33 @@ class KeptKmerDb(CmphKmerDb):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         data = np.ascontiguousarray(data, dtype=STORED_DTYPE)
         _check(lib().skm_db_open_kept(C.byref(self._h), _ptr(keys), _ptr(data), len(keys), device))
+
+
+class DeviceKeptKmerDb(CmphKmerDb):
+    """The KeptKmerDB<8> that SignatureBuilder.kept_db makes on the device (skm_build_kept_db): a
+    range-reduced table of any size, independent of the builder.  lookup_keys returns each key's
+    index in the builder's arena (a permutation of 0..n-1 over the members), hash_size() for a
+    miss.  It holds no records: MatrixDistance over it raises SkmError."""
+
+    def __init__(self, handle, device: int = 0):
+        self._h = handle
+        self.device = device
+
+
+def kept_db_plan(n: int, load_pct: int = 0, slots: int = 0) -> tuple:
+    """skm_kept_db_plan (host only): (slots, bytes) of the table SignatureBuilder.kept_db would
+    allocate for n kept k-mers."""
+    opts = _KeptDbOpts(int(load_pct), 0, int(slots))
+    t, b = C.c_uint64(), C.c_uint64()
+    _check(lib().skm_kept_db_plan(int(n), C.byref(opts), C.byref(t), C.byref(b)))
+    return t.value, b.value
+
+
+def kept_slot(key: int, slots: int) -> int:
+    """skm_debug_kept_slot (host only): the home slot of key in a range-reduced table of `slots`."""
+    v = C.c_uint64()
+    _check(lib().skm_debug_kept_slot(int(key), int(slots), C.byref(v)))
+    return v.value
 
 
 def read_function_index(path: str) -> list:

@@ -68,10 +68,43 @@ __global__ void k_exact_insert(const uint64_t* __restrict__ keys, const uint16_t
     }
 }
 
+// k_exact_insert over the range-reduced table of T slots (kept_home / kept_next), from a build's
+// kept arena in place (10-byte records); its slots are (key low, key high, record word, record
+// index) -- DevBdz::xslots; maxp = the most slots one key examined
+__global__ void k_exactr_insert(const uint64_t* __restrict__ keys, const uint16_t* __restrict__ dat, uint64_t n,
+                                uint4* __restrict__ tab, uint64_t T, uint32_t* __restrict__ bad,
+                                uint32_t* __restrict__ maxp) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long k = keys[i];
+    if (k == 0) {
+        atomicOr(bad, 1u);
+        return;
+    }
+    uint64_t h = kept_home(k, T);
+    // a table with no empty slot left for this key (T <= n, refused on the host) would not end
+    for (uint32_t len = 1;; ++len) {
+        unsigned long long* key = reinterpret_cast<unsigned long long*>(tab + h);
+        const unsigned long long prev = atomicCAS(key, 0ull, k);
+        if (prev == 0ull) {
+            uint32_t* rest = reinterpret_cast<uint32_t*>(tab + h) + 2;
+            rest[0] = ((uint32_t)dat[5 * i + 1] << 16) | (uint32_t)dat[5 * i + 2];  // function_index, mean
+            rest[1] = (uint32_t)i;
+            if (len > *reinterpret_cast<volatile uint32_t*>(maxp)) atomicMax(maxp, len);
+            return;
+        }
+        if (prev == k) {
+            atomicOr(bad, 2u);
+            return;
+        }
+        h = kept_next(h, T);
+    }
+}
 
 // MODE: LK_BDZ7 = BDZ with rank blocks of 128 (cmph's default b = 7), LK_EXACT = kept-k-mer
-// table, LK_BDZ = BDZ with any b (per-window search)
-enum { LK_BDZ7 = 0, LK_EXACT = 1, LK_BDZ = 2 };
+// table, LK_BDZ = BDZ with any b (per-window search), LK_EXACTR = kept-k-mer table, range-reduced
+// (D.xslots slots)
+enum { LK_BDZ7 = 0, LK_EXACT = 1, LK_BDZ = 2, LK_EXACTR = 3 };
 template <int MODE>
 __global__ __launch_bounds__(LK_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k_lookup(const uint8_t* __restrict__ res, uint64_t rp, DevBdz D,
                                                       uint32_t* __restrict__ hits) {
@@ -117,6 +150,46 @@ __global__ __launch_bounds__(LK_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
                     q = D.xtab[h];
                 }
                 out[t] = ((live >> t) & 1u) && (q.x | q.y) != 0u ? q.w : NO_HIT;  // function_index << 16 | mean
+            }
+        } else if constexpr (MODE == LK_EXACTR) {
+            // the same over the range-reduced table: home slot by multiply-high over D.xslots, the
+            // walk wraps at the table's end (64-bit slot indices; the table may pass 2^32 slots).
+            // A probe reads the slot's first 12 bytes, key and record word, in one load; they are kept
+            // as scalars (an array of uint4 stays on the stack, and every probe then waits for its
+            // own load)
+            const uint64_t T = D.xslots;
+            uint32_t sx[LK_POS], sy[LK_POS], sw[LK_POS];
+            uint64_t hp[LK_POS];
+            uint32_t live = 0;
+#pragma unroll
+            for (int t = 0; t < LK_POS; ++t) {
+                const uint64_t p = base + t;
+                uint32_t lo, hi;
+                key_at(w, t, lo, hi);
+                const bool ok = p < rp && ((bad >> t) & 0xFFu) == 0 && ((amb >> (t + 8)) & 1u) == 0;
+                // a window that is not looked up reads slot 0 (always there): a load under a
+                // condition becomes a branch with a wait behind it, and the 16 probes go one by one
+                hp[t] = ok ? kept_home(((uint64_t)hi << 32) | lo, T) : 0ull;
+                const uint4 v = D.xtab[hp[t]];
+                sx[t] = v.x;
+                sy[t] = v.y;
+                sw[t] = v.z;
+                live |= (ok ? 1u : 0u) << t;
+            }
+#pragma unroll
+            for (int t = 0; t < LK_POS; ++t) {
+                uint32_t lo, hi;
+                key_at(w, t, lo, hi);
+                uint32_t qx = sx[t], qy = sy[t], qw = sw[t];
+                uint64_t h = hp[t];
+                while (((live >> t) & 1u) && !(qx == lo && qy == hi) && (qx | qy) != 0u) {
+                    h = kept_next(h, T);
+                    const uint4 v = D.xtab[h];
+                    qx = v.x;
+                    qy = v.y;
+                    qw = v.z;
+                }
+                out[t] = ((live >> t) & 1u) && (qx | qy) != 0u ? qw : NO_HIT;  // function_index << 16 | mean
             }
         } else if constexpr (MODE != LK_BDZ7) {
 #pragma unroll
@@ -1024,6 +1097,22 @@ void db_upload_kept(skm_db* db, const uint64_t* keys, const skm_stored_kmer_data
     }
 }
 
+// hipMalloc of the range-reduced table; a failure names the bytes asked for and the bytes free
+void alloc_kept_table(DevBuf& tab, uint64_t bytes) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        size_t fr = 0, tot = 0;
+        (void)hipMemGetInfo(&fr, &tot);
+        throw Error(e == hipErrorOutOfMemory ? SKM_E_OOM : SKM_E_HIP,
+                    "kept k-mer table: " + std::to_string(bytes) + " bytes asked for, " + std::to_string(fr) +
+                        " bytes free on the device (" + hipGetErrorString(e) + ")");
+    }
+    tab.p = p;
+    tab.bytes = bytes;
+}
+
 bool read_file(const char* path, std::vector<uint8_t>& out) {
     std::ifstream f(path, std::ios::binary);
     if (!f) return false;
@@ -1077,7 +1166,10 @@ void query_run(skm_query* q, const skm_annot_opts* o) {
     if (q->rp && db->m) {
         uint64_t nthreads = ceil_div(q->rp, LK_POS);
         uint32_t grid = (uint32_t)std::min<uint64_t>(ceil_div(nthreads, LK_THREADS), 256ull * 16);
-        if (db->exact)
+        if (db->exact && db->dev.xslots)
+            hipLaunchKernelGGL(k_lookup<LK_EXACTR>, dim3(grid), dim3(LK_THREADS), 0, st, q->d_res.as<uint8_t>(),
+                               q->rp, db->dev, q->d_hits.as<uint32_t>());
+        else if (db->exact)
             hipLaunchKernelGGL(k_lookup<LK_EXACT>, dim3(grid), dim3(LK_THREADS), 0, st, q->d_res.as<uint8_t>(),
                                q->rp, db->dev, q->d_hits.as<uint32_t>());
         else if (db->dev.b == 7)
@@ -1162,7 +1254,81 @@ void query_run(skm_query* q, const skm_annot_opts* o) {
 
 }  // namespace
 
+namespace skm {
+
+uint64_t kept_db_slots(uint64_t n, const skm_kept_db_opts* opts) {
+    const uint32_t pct = opts && opts->load_pct ? opts->load_pct : 40u;  // measured: profiles/kept_db_ab.json
+    SKM_CHECK(pct >= 10 && pct <= 95, SKM_E_ARG, "load_pct must be 0 or 10..95");
+    SKM_CHECK(n < 0xFFFFFFFFull, SKM_E_ARG, "too many kept k-mers for a u32 record index");
+    if (opts && opts->slots) {
+        SKM_CHECK(opts->slots > n, SKM_E_ARG, "slots must exceed the number of keys (the table keeps an empty slot)");
+        SKM_CHECK(opts->slots < (1ull << 59), SKM_E_ARG, "slots out of range");
+        return opts->slots;
+    }
+    return std::max<uint64_t>(16, (100 * n + pct - 1) / pct);
+}
+
+skm_db* db_from_device_kept(const uint64_t* d_keys, const skm_stored_kmer_data* d_data, uint64_t n, uint64_t slots,
+                            int device, hipStream_t st) {
+    SKM_CHECK(n < 0xFFFFFFFFull && slots > n, SKM_E_ARG, "bad kept k-mer table geometry");
+    SKM_HIP(hipSetDevice(device));
+    std::unique_ptr<skm_db, void (*)(skm_db*)> db(new skm_db(), skm_db_close);
+    db->device = device;
+    db->exact = db->ranged = true;
+    db->m = (uint32_t)n;
+    db->dat_records = 0;  // the slots carry the record word; nothing reads the records (D.dat stays null)
+    alloc_kept_table(db->d_xtab, 16 * slots);
+    DevBdz& D = db->dev;
+    D = DevBdz{};
+    D.m = (uint32_t)n;
+    D.xtab = db->d_xtab.as<uint4>();
+    D.xslots = slots;
+    SKM_HIP(hipMemsetAsync(db->d_xtab.p, 0, 16 * slots, st));
+    uint32_t res[2] = {0, 0};  // bad, longest probe
+    if (n) {
+        DevBuf dres;
+        dres.ensure(8);
+        SKM_HIP(hipMemsetAsync(dres.p, 0, 8, st));
+        hipLaunchKernelGGL(k_exactr_insert, dim3((uint32_t)ceil_div(n, 256)), dim3(256), 0, st, d_keys,
+                           reinterpret_cast<const uint16_t*>(d_data), n, db->d_xtab.as<uint4>(), slots,
+                           dres.as<uint32_t>(), dres.as<uint32_t>() + 1);
+        SKM_HIP(hipGetLastError());
+        SKM_HIP(hipMemcpyAsync(res, dres.p, 8, hipMemcpyDeviceToHost, st));
+    }
+    SKM_HIP(hipStreamSynchronize(st));
+    SKM_CHECK(!(res[0] & 1u), SKM_E_ARG, "kept k-mer key 0 is not a valid k-mer");
+    SKM_CHECK(!(res[0] & 2u), SKM_E_ARG, "duplicate kept k-mer keys");
+    db->max_probe = res[1];
+    return db.release();
+}
+
+}  // namespace skm
+
 extern "C" {
+
+int skm_kept_db_plan(uint64_t n, const skm_kept_db_opts* opts, uint64_t* slots, uint64_t* bytes) {
+    SKM_API_BEGIN
+    const uint64_t T = kept_db_slots(n, opts);
+    if (slots) *slots = T;
+    if (bytes) *bytes = 16 * T;
+    SKM_API_END
+}
+
+int skm_debug_kept_slot(uint64_t key, uint64_t slots, uint64_t* slot) {
+    SKM_API_BEGIN
+    SKM_CHECK(slot && slots, SKM_E_ARG, "bad argument");
+    *slot = kept_home(key, slots);
+    SKM_API_END
+}
+
+int skm_db_table_info(skm_db* db, uint64_t* out, int cap) {
+    if (!db || !out) return SKM_E_ARG;
+    const uint64_t T = !db->exact ? 0 : db->ranged ? db->dev.xslots : db->dev.xmask + 1;
+    const uint64_t v[5] = {T, 16 * T, db->exact ? (uint64_t)db->m : 0, db->max_probe, db->ranged ? 1u : 0u};
+    const int n = std::min(cap, 5);
+    for (int i = 0; i < n; ++i) out[i] = v[i];
+    return n;
+}
 
 int skm_db_open_mem(skm_db** out, const uint8_t* mph, size_t mph_len, const uint8_t* dat, size_t dat_len, int device) {
     SKM_API_BEGIN
@@ -1219,14 +1385,36 @@ int skm_db_size(skm_db* db, uint32_t* m) {
 }
 
 extern "C++" {
-// mode 0: exact table; 1: generic bdz_search (any b); 2: the (g word, rank) pair lines (b == 7)
+// mode 0: exact table; 1: generic bdz_search (any b); 2: the (g word, rank) pair lines (b == 7);
+// 3: exact table, range-reduced
 template <int MODE>
 __global__ void k_lookup_keys(const uint64_t* __restrict__ keys, uint64_t n, DevBdz D, uint32_t* __restrict__ out) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint64_t k = keys[i];
     const uint32_t lo = (uint32_t)k, hi = (uint32_t)(k >> 32);
-    out[i] = MODE == 0 ? exact_lookup(D, lo, hi) : MODE == 1 ? bdz_lookup(D, lo, hi) : bdz7_lookup(D, lo, hi);
+    if constexpr (MODE == 3) {
+        const uint4 t = exactr_slot(D, lo, hi);
+        out[i] = (t.x | t.y) ? t.z : D.m;
+    } else {
+        out[i] = MODE == 0 ? exact_lookup(D, lo, hi) : MODE == 1 ? bdz_lookup(D, lo, hi) : bdz7_lookup(D, lo, hi);
+    }
+}
+// skm_db_lookup_fm: the record word the call path reads for each key (exact: from the key's slot
+// on either table; BDZ: the record the search lands on), NO_HIT for a miss
+template <bool EXACT>
+__global__ void k_lookup_fm(const uint64_t* __restrict__ keys, uint64_t n, DevBdz D, uint32_t* __restrict__ out) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t k = keys[i];
+    const uint32_t lo = (uint32_t)k, hi = (uint32_t)(k >> 32);
+    if constexpr (EXACT) {
+        const uint4 t = k ? exact_any_slot(D, lo, hi) : make_uint4(0u, 0u, 0u, 0u);  // 0 marks an empty slot
+        out[i] = (t.x | t.y) ? t.w : NO_HIT;
+    } else {
+        const uint32_t idx = D.blk ? bdz7_lookup(D, lo, hi) : bdz_lookup(D, lo, hi);
+        out[i] = idx < D.m ? D.fm[idx] : NO_HIT;
+    }
 }
 }  // extern "C++"
 
@@ -1245,7 +1433,9 @@ static int db_lookup(skm_db* db, const uint64_t* keys, size_t n, uint32_t* idx_o
     SKM_HIP(hipMemcpy(dk.p, keys, 8 * n, hipMemcpyHostToDevice));
     const dim3 grid((uint32_t)ceil_div(n, 256)), blk(256);
     // the same search the annotate / matrix kernels run: pair lines whenever the DB has them
-    if (db->exact)
+    if (db->exact && db->dev.xslots)
+        hipLaunchKernelGGL(k_lookup_keys<3>, grid, blk, 0, 0, dk.as<uint64_t>(), (uint64_t)n, db->dev, dout.as<uint32_t>());
+    else if (db->exact)
         hipLaunchKernelGGL(k_lookup_keys<0>, grid, blk, 0, 0, dk.as<uint64_t>(), (uint64_t)n, db->dev, dout.as<uint32_t>());
     else if (db->dev.blk && !generic)
         hipLaunchKernelGGL(k_lookup_keys<2>, grid, blk, 0, 0, dk.as<uint64_t>(), (uint64_t)n, db->dev, dout.as<uint32_t>());
@@ -1262,6 +1452,29 @@ int skm_db_lookup(skm_db* db, const uint64_t* keys, size_t n, uint32_t* idx_out)
 
 int skm_debug_db_lookup_generic(skm_db* db, const uint64_t* keys, size_t n, uint32_t* idx_out) {
     return db_lookup(db, keys, n, idx_out, true);
+}
+
+int skm_db_lookup_fm(skm_db* db, const uint64_t* keys, size_t n, uint32_t* fm_out) {
+    SKM_API_BEGIN
+    SKM_CHECK(db && (n == 0 || (keys && fm_out)), SKM_E_ARG, "null argument");
+    if (n == 0) return SKM_OK;
+    SKM_HIP(hipSetDevice(db->device));
+    if (db->m == 0) {
+        for (size_t i = 0; i < n; ++i) fm_out[i] = NO_HIT;
+        return SKM_OK;
+    }
+    DevBuf dk, dout;
+    dk.ensure(8 * n);
+    dout.ensure(4 * n);
+    SKM_HIP(hipMemcpy(dk.p, keys, 8 * n, hipMemcpyHostToDevice));
+    const dim3 grid((uint32_t)ceil_div(n, 256)), blk(256);
+    if (db->exact)
+        hipLaunchKernelGGL(k_lookup_fm<true>, grid, blk, 0, 0, dk.as<uint64_t>(), (uint64_t)n, db->dev, dout.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(k_lookup_fm<false>, grid, blk, 0, 0, dk.as<uint64_t>(), (uint64_t)n, db->dev, dout.as<uint32_t>());
+    SKM_HIP(hipGetLastError());
+    SKM_HIP(hipMemcpy(fm_out, dout.p, 4 * n, hipMemcpyDeviceToHost));
+    SKM_API_END
 }
 
 void skm_db_close(skm_db* db) {

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "skm_common.h"
+#include "skm_keptdb.h"
 #include "skm_pool.h"
 #include "skm_output.h"
 #include "skm_util.h"
@@ -5216,6 +5217,7 @@ struct skm_build {
     uint64_t n_windows = 0;
     bool seqid_strict = true;
     bool prepared = false, ran = false;
+    bool work_released = false;         // skm_build_kept_db(release_work): only the results are left
 
     // device input
     DevBuf d_res, d_meta, d_blk2seq, d_glen;
@@ -6126,7 +6128,15 @@ void route_plan(const Ranks& bs) {
     }
 }
 
+void check_not_released(const Ranks& bs) {
+    for (auto* b : bs)
+        SKM_CHECK(!b->work_released, SKM_E_STATE,
+                  "the build's work buffers were released (skm_build_kept_db release_work): the handle can only be "
+                  "read out and destroyed");
+}
+
 void prepare(const Ranks& bs) {
+    check_not_released(bs);
     bool need = false;
     for (auto* b : bs) need |= !b->prepared;
     if (!need) return;
@@ -7316,6 +7326,7 @@ void run_once(const Ranks& bs) {
 }
 
 void run_ranks(const Ranks& bs) {
+    check_not_released(bs);
     prepare(bs);
     for (int attempt = 0;; ++attempt) {
         run_once(bs);
@@ -7424,6 +7435,7 @@ int skm_build_add_batch(skm_build* b, const uint8_t* residues, const uint64_t* s
     SKM_API_BEGIN
     SKM_CHECK(b, SKM_E_ARG, "null build");
     SKM_CHECK(n_seqs == 0 || (residues && seq_off && seq_len && seq_func), SKM_E_ARG, "null array");
+    check_not_released(Ranks{b});
     SKM_HIP(hipSetDevice(b->device));
     const auto t0 = std::chrono::steady_clock::now();
     // the batch's kept sequences (signature_build.tcc:155-158 skips the others), validated
@@ -7512,6 +7524,7 @@ int skm_build_add_batch(skm_build* b, const uint8_t* residues, const uint64_t* s
 int skm_build_reserve(skm_build* b, uint64_t n_residues, uint64_t n_seqs) {
     SKM_API_BEGIN
     SKM_CHECK(b, SKM_E_ARG, "null build");
+    check_not_released(Ranks{b});
     SKM_HIP(hipSetDevice(b->device));
     res_reserve(b, n_residues + n_seqs + 64);
     b->h_meta.reserve(n_seqs);
@@ -8170,6 +8183,46 @@ int skm_build_signature_flags(skm_build* b, uint8_t* out, uint64_t cap) {
     SKM_HIP(hipSetDevice(b->device));
     const uint64_t n = std::min<uint64_t>(cap, b->n_total);
     if (n) SKM_HIP(hipMemcpy(out, b->d_flags.p, n, hipMemcpyDeviceToHost));
+    SKM_API_END
+}
+
+// skm_build_kept_db(release_work): every device buffer but what finish, finish_slice,
+// signature_flags and counters read -- the kept arena (d_keys, d_data), the statistics (d_ctr,
+// d_dfunc, d_swf) and the signature flags (d_flags) -- once nothing of the run is in flight
+static void release_work(skm_build* b) {
+    SKM_HIP(hipDeviceSynchronize());
+    b->tail_issue = nullptr;
+    DevBuf* work[] = {
+        &b->d_res, &b->d_meta, &b->d_blk2seq, &b->d_glen, &b->d_hist, &b->d_offs, &b->d_partial, &b->d_rbbase,
+        &b->d_bstart32, &b->d_bstart, &b->d_owner_start, &b->d_recs_hi, &b->d_recs_lo, &b->d_tmp_hi, &b->d_tmp_lo,
+        &b->d_stg_hi, &b->d_stg_lo, &b->d_part_order, &b->d_cur0, &b->d_cur1, &b->d_slices, &b->d_flagbits,
+        &b->d_chainq, &b->d_ovf, &b->d_ovf_hi, &b->d_ovf_lo, &b->d_ovf_heads, &b->d_ovf_job, &b->d_ovf_fm, &b->d_jobs,
+        &b->d_lens, &b->d_stamps, &b->d_big_desc, &b->d_big_out, &b->d_rhi, &b->d_rlo, &b->d_cnt_send, &b->d_cnt_recv,
+        &b->d_seg_start, &b->d_seg_len, &b->d_vstart, &b->d_xs, &b->d_hv_keys, &b->d_hv_rec, &b->d_hv_len, &b->d_hv_s0,
+        &b->d_hv_s1, &b->d_sub_tab, &b->d_jobs2, &b->d_jobs3, &b->d_ids, &b->d_bloom, &b->d_posg, &b->d_histg,
+        &b->d_npos, &b->d_selrows, &b->d_seloff, &b->d_recs_hi2, &b->d_recs_lo2, &b->d_tmp_hi2, &b->d_tmp_lo2,
+        &b->d_ovf2b, &b->d_gstat, &b->d_long_arena, &b->d_long_jobs, &b->d_ovf2, &b->d_plan, &b->d_run};
+    for (DevBuf* d : work) d->release();
+    for (ChainSet* cs : {&b->cs_main, &b->cs_ovf, &b->cs_ovf3})
+        for (DevBuf* d : {&cs->hist, &cs->offs, &cs->sorted, &cs->long_off}) d->release();
+    for (auto* q : {&b->gsamples, &b->gjobs, &b->gcount})
+        for (DevBuf& d : *q) d.release();
+    b->work_released = true;
+}
+
+int skm_build_kept_db(skm_build* b, const skm_kept_db_opts* opts, skm_db** out) {
+    SKM_API_BEGIN
+    SKM_CHECK(b && out, SKM_E_ARG, "null argument");
+    *out = nullptr;
+    SKM_CHECK(b->world == 1, SKM_E_STATE,
+              "skm_build_kept_db needs world_size 1: the kept set of a multi-rank build is sharded over the ranks");
+    (void)kept_db_slots(0, opts);  // argument errors before any work
+    SKM_HIP(hipSetDevice(b->device));
+    if (!b->prepared || !b->ran) run_ranks(Ranks{b});
+    const uint64_t slots = kept_db_slots(b->n_kept, opts);
+    if (opts && opts->release_work && !b->work_released) release_work(b);
+    *out = db_from_device_kept(b->d_keys.as<uint64_t>(), b->d_data.as<skm_stored_kmer_data>(), b->n_kept, slots,
+                               b->device, b->stream);
     SKM_API_END
 }
 

@@ -83,6 +83,17 @@ int skm_device_count(int* n) {
     SKM_API_END
 }
 
+int skm_device_mem_info(int device, uint64_t* free_bytes, uint64_t* total_bytes) {
+    SKM_API_BEGIN
+    SKM_CHECK(free_bytes && total_bytes, SKM_E_ARG, "null argument");
+    SKM_HIP(hipSetDevice(device));
+    size_t fr = 0, tot = 0;
+    SKM_HIP(hipMemGetInfo(&fr, &tot));
+    *free_bytes = fr;
+    *total_bytes = tot;
+    SKM_API_END
+}
+
 int skm_find_best_call(const skm_kmer_call* calls_in, size_t ncalls, const char* const* function_index, size_t nfunc,
                        uint16_t* out_fi, float* out_score, float* out_offset, char* out_func, size_t out_func_cap) {
     SKM_API_BEGIN

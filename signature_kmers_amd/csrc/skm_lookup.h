@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "skm_bdz.h"
+#include "skm_keptdb.h"
 #include "skm_util.h"
 
 namespace skm {
@@ -40,9 +41,15 @@ struct DevBdz {
     const uint4* xtab;                // [mask+1]
     uint64_t xmask;
     uint32_t xshift;
+    // range-reduced exact table (skm_build_kept_db): xslots != 0 slots, any count (not a power of
+    // two, possibly > 2^32); home slot kept_home(key, xslots), the next slot wraps at xslots; xmask
+    // and xshift are unused.  Its slots hold z = the record word and w = the record index, the
+    // other way round: the annotate probe needs x, y and the record word, which is then one
+    // 12-byte load (with the word in w the compiler splits the probe into an 8- and a 4-byte load)
+    uint64_t xslots;
 };
 
-__device__ __forceinline__ uint64_t xmix(uint64_t k) {  // murmur3 fmix64 (bijective)
+__host__ __device__ __forceinline__ uint64_t xmix(uint64_t k) {  // murmur3 fmix64 (bijective)
     k ^= k >> 33;
     k *= 0xff51afd7ed558ccdull;
     k ^= k >> 33;
@@ -65,6 +72,33 @@ __device__ __forceinline__ uint4 exact_slot(const DevBdz& D, uint32_t lo, uint32
 __device__ __forceinline__ uint32_t exact_lookup(const DevBdz& D, uint32_t lo, uint32_t hi) {
     const uint4 t = exact_slot(D, lo, hi);
     return (t.x | t.y) ? t.z : D.m;
+}
+
+// the range-reduced table's home slot of a key among T slots: the high 64 bits of xmix(key) * T
+// (multiply-high range reduction, uniform for any T; all arithmetic 64-bit, T may exceed 2^32).
+// The one function of the insert kernel, the lookups and skm_debug_kept_slot.
+__host__ __device__ __forceinline__ uint64_t kept_home(uint64_t key, uint64_t T) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(xmix(key), T);
+#else
+    return (uint64_t)(((unsigned __int128)xmix(key) * T) >> 64);
+#endif
+}
+__host__ __device__ __forceinline__ uint64_t kept_next(uint64_t h, uint64_t T) { return h + 1 == T ? 0 : h + 1; }
+
+// exact_slot over the range-reduced table (D.xslots slots; it always holds an empty slot),
+// returned in exact_slot's order: z = the record index, w = the record word
+__device__ __forceinline__ uint4 exactr_slot(const DevBdz& D, uint32_t lo, uint32_t hi) {
+    uint64_t h = kept_home(((uint64_t)hi << 32) | lo, D.xslots);
+    for (;;) {
+        const uint4 t = D.xtab[h];
+        if ((t.x == lo && t.y == hi) || (t.x | t.y) == 0u) return make_uint4(t.x, t.y, t.w, t.z);
+        h = kept_next(h, D.xslots);
+    }
+}
+// the per-key lookups' slot search on either exact table
+__device__ __forceinline__ uint4 exact_any_slot(const DevBdz& D, uint32_t lo, uint32_t hi) {
+    return D.xslots ? exactr_slot(D, lo, hi) : exact_slot(D, lo, hi);
 }
 
 __device__ __forceinline__ uint32_t fastmod(uint32_t a, uint64_t M, uint32_t d) {
@@ -172,7 +206,9 @@ struct skm_query;
 struct skm_db {
     skm_query* aq = nullptr;     // skm_annotate's query, reused call to call (its buffers, stream)
     int device = 0;
-    bool exact = false;          // KeptKmerDB semantics (skm_db_open_kept)
+    bool exact = false;          // KeptKmerDB semantics (skm_db_open_kept, skm_build_kept_db)
+    bool ranged = false;         // exact, range-reduced table without the records (skm_build_kept_db)
+    uint32_t max_probe = 0;      // ranged: slots the longest insert examined
     uint32_t m = 0;              // hash size (BDZ) or number of kept keys (exact)
     skm::Bdz bdz;
     uint64_t dat_records = 0;

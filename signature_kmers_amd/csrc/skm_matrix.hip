@@ -1357,6 +1357,8 @@ int skm_matrix_create(skm_matrix** out, skm_db* db, const uint8_t* residues, con
                       const uint32_t* seq_len, const uint32_t* seq_idx, size_t n_seqs, uint32_t n_idx) {
     SKM_API_BEGIN
     SKM_CHECK(out && db, SKM_E_ARG, "null argument");
+    SKM_CHECK(!db->ranged, SKM_E_ARG,
+              "matrix distance needs the DB's records; a DB made by skm_build_kept_db holds only its table");
     SKM_CHECK(n_seqs == 0 || (residues && seq_off && seq_len && seq_idx), SKM_E_ARG, "null array");
     SKM_CHECK(n_seqs < 0xFFFFFFFFull, SKM_E_ARG, "too many sequences in one batch");
     for (size_t s = 0; s < n_seqs; ++s) SKM_CHECK(seq_idx[s] < n_idx, SKM_E_ARG, "seq_idx out of range");
@@ -1481,6 +1483,8 @@ int skm_matrix_batch_create(skm_matrix_batch** out, skm_db* db, const uint8_t* r
                             const uint32_t* prob_nidx, size_t n_prob) {
     SKM_API_BEGIN
     SKM_CHECK(out && db, SKM_E_ARG, "null argument");
+    SKM_CHECK(!db->ranged, SKM_E_ARG,
+              "matrix distance needs the DB's records; a DB made by skm_build_kept_db holds only its table");
     SKM_CHECK(n_prob == 0 || (prob_seq && prob_nidx), SKM_E_ARG, "null array");
     SKM_CHECK(n_prob < 0xFFFFFFFFull, SKM_E_ARG, "too many problems in one batch");
     const uint64_t n_seqs = n_prob ? prob_seq[n_prob] : 0;

@@ -175,7 +175,7 @@ int main(int argc, char** argv) {
                 {"help", 'h', true, false},            {"device", 0, false, false},
                 {"dump-extract", 0, false, false},     {"mph-seed", 0, false, false},
                 {"n-gpus", 0, false, false},           {"comm", 0, false, false},
-                {"comm-file", 0, false, false}};
+                {"comm-file", 0, false, false},        {"recall-db", 0, false, false}};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
     if (op.has("help")) {
@@ -197,6 +197,8 @@ int main(int argc, char** argv) {
                   << "  --n-gpus arg                         ranks (one process and GPU each, power of two)\n"
                   << "  --comm arg                           rccl (default) or host (socketpairs; ranks may share a GPU)\n"
                   << "  --comm-file arg                      RCCL id rendezvous file under an external launcher\n"
+                  << "  --recall-db arg                      host (default): the recall DB from the downloaded kept k-mers;\n"
+                  << "                                       device: built on the GPU from the build's resident kept k-mers (one GPU)\n"
                   << "  -h [ --help ]                        show this help message\n";
         return 1;
     }
@@ -206,8 +208,12 @@ int main(int argc, char** argv) {
     Mesh mesh;
     const std::string comm = op.get("comm", "rccl");
     if (comm != "rccl" && comm != "host") die("--comm must be rccl or host");
+    const std::string recall_db = op.get("recall-db", "host");
+    if (recall_db != "host" && recall_db != "device") die("--recall-db must be host or device");
     const char* env_ws = std::getenv("WORLD_SIZE");
     const bool launched = env_ws && std::atoi(env_ws) > 1 && !op.has("n-gpus");
+    if (recall_db == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
+        die("--recall-db device needs one GPU: the kept k-mers of a multi-rank build are sharded over the ranks");
     int local_rank = 0;
     if (launched) {
         if (comm == "host") die("--comm host needs --n-gpus (forked ranks)");
@@ -432,6 +438,14 @@ int main(int argc, char** argv) {
     float ph[12] = {0};
     int nph = skm_build_last_timings(b, ph, 12);
     const double t_build = t_prepare + t_run + t_finish;
+    // --recall-db device: the recall DB from the arena while the handle still holds it (the work
+    // buffers go first: the table needs their room at the headline size)
+    skm_db* kdb = nullptr;
+    if (recall_db == "device") {
+        skm_kept_db_opts ko{};
+        ko.release_work = 1;
+        check(skm_build_kept_db(b, &ko, &kdb), "skm_build_kept_db");
+    }
     skm_build_destroy(b);
     if (rank != 0) {  // rank 0 holds every kept k-mer and the all-reduced statistics
         skm_kept_free(&kept);
@@ -491,8 +505,7 @@ int main(int argc, char** argv) {
     if (!read_function_index(fi_file, fidx, err)) die(err);
     std::cerr << "Begin recall\n";
     t0 = now_s();
-    skm_db* kdb = nullptr;
-    check(skm_db_open_kept(&kdb, kept.keys, kept.data, kept.n, device), "skm_db_open_kept");
+    if (!kdb) check(skm_db_open_kept(&kdb, kept.keys, kept.data, kept.n, device), "skm_db_open_kept");
     std::vector<const FastaFile*> fptr;
     for (auto& f : files) fptr.push_back(&f);
     std::vector<std::vector<SeqCall>> calls;
