@@ -971,6 +971,49 @@ int64_t oracle_matrix_distance(const oracle_bdz* db, const oracle_stored* dat, c
     return (int64_t)n;
 }
 
+// The same against the exact kept-k-mer DB (KeptKmerDB::fetch, kept_kmer_db.h:20-27: a window that
+// is no key makes no callback): keys sorted ascending, data[i] the record of keys[i].
+int64_t oracle_matrix_distance_exact(const uint64_t* keys, const oracle_stored* data, uint64_t nkeys,
+                                     const uint8_t* residues, const uint64_t* seq_off, const uint32_t* seq_len,
+                                     const uint32_t* seq_idx, uint64_t n_seqs, int32_t hypo_index, uint32_t* out,
+                                     uint64_t cap) {
+    std::map<uint64_t, std::vector<uint32_t>> hit_map;
+    for (uint64_t s = 0; s < n_seqs; ++s) {
+        const double seqlen = static_cast<double>(seq_len[s]);
+        for_each_kmer8(residues + seq_off[s], seq_len[s], [&](const uint8_t* ptr, size_t) {
+            const uint64_t key = load_key(ptr);
+            const uint64_t* it = std::lower_bound(keys, keys + nkeys, key);
+            if (it == keys + nkeys || *it != key) return;
+            const oracle_stored& kd = data[it - keys];
+            if (hypo_index >= 0 && kd.function_index == (uint16_t)hypo_index) return;
+            const double mean = static_cast<double>(kd.mean);
+            const double stddev = kd.var == 0 ? seqlen * 0.1 : std::sqrt(static_cast<double>(kd.var));
+            const double cutoff_b = mean - stddev * 2.0;
+            const double cutoff_t = mean + stddev * 2.0;
+            if (seqlen < cutoff_b || seqlen > cutoff_t) return;
+            hit_map[key].push_back(seq_idx[s]);
+        });
+    }
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> dist;
+    for (auto& kv : hit_map) {
+        std::vector<uint32_t>& v = kv.second;
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        for (size_t a = 0; a < v.size(); ++a)
+            for (size_t b = a + 1; b < v.size(); ++b) dist[{v[a], v[b]}]++;
+    }
+    uint64_t n = 0;
+    for (auto& kv : dist) {
+        if (n < cap) {
+            out[3 * n] = kv.first.first;
+            out[3 * n + 1] = kv.first.second;
+            out[3 * n + 2] = kv.second;
+        }
+        ++n;
+    }
+    return (int64_t)n;
+}
+
 // The same pair counts on n_threads host threads (bench.py's CPU baseline of the matrix leg; the
 // reference fills kmer_hit_map from process_fasta_stream_parallel's TBB tasks, matrix_distance.h
 // :130-143).  (1) threads over sequence ranges collect (kmer, index) hits; (2) threads over k-mer

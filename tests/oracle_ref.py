@@ -60,6 +60,9 @@ def olib():
         _lib.oracle_annotate_mt.argtypes = [P, P, P, P, P, C.c_uint64, C.POINTER(AnnotOpts), C.c_int]
         _lib.oracle_matrix_distance.restype = C.c_int64
         _lib.oracle_matrix_distance.argtypes = [P, P, P, P, P, P, C.c_uint64, C.c_int32, P, C.c_uint64]
+        _lib.oracle_matrix_distance_exact.restype = C.c_int64
+        _lib.oracle_matrix_distance_exact.argtypes = [P, P, C.c_uint64, P, P, P, P, C.c_uint64, C.c_int32, P,
+                                                      C.c_uint64]
         _lib.oracle_matrix_distance_mt.restype = C.c_int64
         _lib.oracle_matrix_distance_mt.argtypes = [P, P, P, P, P, P, C.c_uint64, C.c_int32, P, C.c_uint64, C.c_int]
         _lib.oracle_kmer_windows.restype = C.c_uint32
@@ -387,6 +390,23 @@ def matrix_distance(bdz: Bdz, dat: bytes, residues, seq_off, seq_len, seq_idx, h
     out = np.zeros((max(n, 1), 3), np.uint32)
     L.oracle_matrix_distance(bdz.h, _p(datb), _p(residues), _p(seq_off), _p(seq_len), _p(seq_idx), len(seq_len),
                              hypo_index, _p(out), n)
+    return out[:n].copy()
+
+
+def matrix_distance_exact(keys, data, residues, seq_off, seq_len, seq_idx, hypo_index=-1):
+    """matrix_distance() against KeptKmerDB (exact keys; keys sorted ascending, data[i] for keys[i])."""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    data = np.ascontiguousarray(data, STORED_DTYPE)
+    residues = np.ascontiguousarray(residues, np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, np.uint64)
+    seq_len = np.ascontiguousarray(seq_len, np.uint32)
+    seq_idx = np.ascontiguousarray(seq_idx, np.uint32)
+    L = olib()
+    args = (_p(keys), _p(data), len(keys), _p(residues), _p(seq_off), _p(seq_len), _p(seq_idx), len(seq_len),
+            hypo_index)
+    n = int(L.oracle_matrix_distance_exact(*args, None, 0))
+    out = np.zeros((max(n, 1), 3), np.uint32)
+    L.oracle_matrix_distance_exact(*args, _p(out), n)
     return out[:n].copy()
 
 

@@ -6,6 +6,7 @@ reference lines:
   build_py        signature_build.tcc:121-181 (windows), :184-213 (group visit), :219-293 (cut/stats)
   P2              Boost.Accumulators p_square_quantile, p = 0.5
   call_windows    for_each_kmer, kmer_data.h:76-102
+  hitset_calls    process_aa_seq and HitSet::process, call_functions.tcc:259-338, :35-103
 Parity with the reference itself is unpinned: the reference ships no fixtures.
 """
 from __future__ import annotations
@@ -176,3 +177,91 @@ def matrix_distance(seqs, seq_idx, fetch, hypo_index):
             for b in range(a + 1, len(v)):
                 dist[(v[a], v[b])] = dist.get((v[a], v[b]), 0) + 1
     return dist
+
+
+def _bm_mean(vals, mean_mode):
+    """boost::math::statistics::mean over float32 values in hit order: the four-lane form of
+    Boost >= 1.76 (mean_mode 0) or the single running mean (mean_mode 1), every step rounded to
+    float32."""
+    import numpy as np
+    F = np.float32
+    n = len(vals)
+    if mean_mode == 1:
+        mu, i = F(0), F(1)
+        for x in vals:
+            mu = mu + (x - mu) / i
+            i = i + F(1)
+        return mu
+    end = n - n % 4
+    mu = [F(0), F(0), F(0), F(0)]
+    i = F(1)
+    for it in range(0, end, 4):
+        inv = F(1) / i
+        for j in range(4):
+            mu[j] = mu[j] + (vals[it + j] - mu[j]) * inv
+        i = i + F(1)
+    num1 = F(end) / F(4)
+    num2 = num1 + F(n % 4)
+    for it in range(end, n):  # the tail runs on lane 3
+        mu[3] = mu[3] + (vals[it] - mu[3]) / i
+        i = i + F(1)
+    return (num1 * (mu[0] + mu[1] + mu[2]) + num2 * mu[3]) / F(n)
+
+
+def hitset_calls(length, hits, min_hits, max_gap, ignore_hypo, hypo_index, mean_mode):
+    """process_aa_seq and HitSet::process (call_functions.tcc:259-338, :35-103) over one sequence of
+    `length` residues whose DB hits are `hits`: (window position, function_index, mean) in window
+    order.  Returns the calls as (start, end, count, function_index, median as unsigned, MAD as
+    numpy.float32).
+
+    The statistics are Boost.Math's on std::vector<float>: the mean as _bm_mean, the median and the
+    MAD as order statistics of the sorted values and of |float(x) - median| (the corrected MAD,
+    mad_mode 0; the older one depends on libstdc++'s nth_element permutation and is left to the C++
+    oracle), mad == 0 -> 30, the cut-offs mean -/+ 2 mad in double.  min_hits >= 2: with one hit
+    the reference's process() reads end[1] before the beginning of its vector."""
+    import numpy as np
+    F = np.float32
+    assert min_hits >= 2
+    calls = []
+    held = []      # the HitSet: (pos, function_index, mean)
+    cur = 0xFFFF   # UndefinedFunction
+    seqlen = float(length)
+
+    def process():
+        nonlocal cur, held
+        mine = [h for h in held if h[1] == cur]
+        vals = [F(h[2]) for h in mine]
+        n = len(vals)
+        mean = _bm_mean(vals, mean_mode)
+        srt = np.sort(np.array(vals, F))
+        median = srt[(n - 1) // 2] if n & 1 else (srt[n // 2 - 1] + srt[n // 2]) / F(2)
+        dev = np.sort(np.abs(srt - median))
+        mad = dev[(n - 1) // 2] if n & 1 else (dev[n // 2 - 1] + dev[n // 2]) / F(2)
+        if mad == 0:
+            mad = F(30)
+        cutoff_b = float(mean) - 2.0 * float(mad)
+        cutoff_t = float(mean) + 2.0 * float(mad)
+        if n >= min_hits and not (seqlen < cutoff_b or seqlen > cutoff_t):
+            calls.append((held[0][0], mine[-1][0] + 7, n, cur, int(median), F(mad)))
+        if held[-2][1] != cur and held[-2][1] == held[-1][1]:
+            cur = held[-2][1]
+            held = held[-2:]
+        else:
+            held = []
+
+    for pos, func, mean in hits:
+        if ignore_hypo and func == hypo_index:
+            continue
+        if held and held[-1][0] + max_gap < pos:
+            if len(held) >= min_hits:
+                process()
+            else:
+                held = []
+        if not held:
+            cur = func
+        held.append((pos, func, mean))
+        if len(held) > 1 and cur != func and held[-2][1] == held[-1][1]:
+            process()
+    if len(held) >= min_hits:
+        process()
+    return calls
