@@ -164,8 +164,8 @@ int skm_build_kernel_timings(skm_build* b, char* names, size_t names_cap, float*
  * host pool, [36] chunks, and its device microseconds summed over the chunks: [37] selection,
  * [38] radix sort, [39] gather, [40] the D2H pieces; [41] the largest hand-off chunk (k-mers),
  * [42] 1 if the hand-off used 64-bit arena indices (>= 2^32 k-mers); [43] the kept arena's
- * capacity (k-mers); [44] device bytes free after prepare; [45] 1 if the passes alternate two
- * element buffers ("recs_rot"); [46] overflow sub-buckets whose light remainder (what is left once
+ * capacity (k-mers); [44] device bytes free after prepare; [45] reserved, always 0 (it keeps
+ * the places of the slots after it); [46] overflow sub-buckets whose light remainder (what is left once
  * the heavy k-mers are split off, at most 2048 occurrences) was grouped by the LDS hash path
  * (k_ovf_light) instead of the overflow sort, [47] the occurrences in them (both 0 with
  * "ovf_light" 0; their kept k-mers count in [8], those of their groups of > 64 members in [10]);
@@ -234,34 +234,23 @@ int skm_debug_transport_check(const skm_transport* tp, int rank, int world);
  *   below four passes: 1 = on, 0 = off; default on at world_size > 1), "route_first_min" (its
  *   occurrence threshold, 131072), "tail_async" (one GPU, key-range passes: a pass's big groups,
  *   chains and accounting on their own stream beside the next pass's staging; 1),
- *   "stage_round" (key-range
- *   passes: 1 = the staged position scatter in half rounds of 2048 elements, four workgroups
- *   per CU, the default; 0 = rounds of 4096), "partition_round"
- *   (k_partition staging rounds: 0 = 2048 elements, three 512-thread workgroups per CU (default);
- *   1 = 4096, one per CU; 2 = 4096, one 1024-thread workgroup per CU), "flag_check" (1: the
- *   group-by reads a sequence's signature flag before storing it; 0), "serial_overflow"
+ *   "stage_round" (key-range passes: 1 = the staged position scatter in half rounds of 2048
+ *   elements, four workgroups per CU, the default; 0 = rounds of 4096), "serial_overflow"
  *   (diagnostics: 1 = a pass's overflow path starts after its group-by kernel; 0), "chain_cus"
  *   (the stashed long chains' stream confined to this many CUs, a multiple of 8; 0 = all),
- *   "side_cus" (the same for the overflow streams and the next pass's selection), "overlap"
- *   (key-range passes on one GPU: 1 = pipelined passes -- a second element buffer set when it
- *   fits, so a pass's overflow path runs beside the next pass's extract and partition; 0 = each
- *   pass waits for its overflow path, the default), "heavy_grid" (k_heavy's persistent grid, 512),
+ *   "side_cus" (the same for the overflow streams and the next pass's selection),
+ *   "big_split" (tail_async: the two big-group size classes on two tail streams; 0),
+ *   "heavy_grid" (k_heavy's persistent grid, 512),
  *   "lane_long" (key-range passes: stashed long chains below this many samples run one lane each,
  *   64 chains per wave, instead of on a wave pair; 2^20; 0 = all on wave pairs), "lane_grid"
  *   (their grid, 256), "lane_tail" (the threshold for the batch after the last pass, 2^16),
- *   "lane_streams" (their batches rotate over 1..4 streams, 1), "chain_queue" (1: chain waves take
- *   64-job blocks from a work queue instead of a fixed stride), "flag_bits" (1: signature flags
- *   kept as bits during the run, read before an atomic set; 0: a byte store per kept
- *   occurrence), "sub_target" (k_partition's target elements per level-2 sub-bucket; 0 = 768),
- *   "big_split" (tail_async: the two big-group size classes on two tail streams; 0),
+ *   "lane_streams" (their batches rotate over 1..4 streams, 1),
+ *   "sub_target" (k_partition's target elements per level-2 sub-bucket; 0 = 768),
+ *   "part_order" (k_partition's workgroups take the buckets of more than twice the mean size
+ *   first; 1), "big_grid" / "big_grid_large" (k_big_groups' persistent grids),
  *   "emit_group" (key-range passes emitted per residue scan: 0 = 4, or 1, 2, 4, 8, 16),
- *   "tail_defer" (tail_async: a pass's tail issued after the next pass's scan kernels; 0),
- *   "recs_rot" (tail_async: the passes alternate two element buffers, so a split does not wait
- *   for the previous pass's tail; +16 B per element of the largest pass when it fits; 0),
  *   "handoff_index_limit" / "handoff_max_chunk" (tests: force the hand-off's 64-bit indices /
- *   small chunks),
- *   "diag" (diagnostics only, wrong results: skips of flag stores / the heavy sort / chain
- *   kernels / overflow entry classes).
+ *   small chunks).
  * Unknown names and out-of-range values return SKM_E_ARG. */
 int skm_build_set_option(skm_build* b, const char* name, int64_t value);
 /* Diagnostics: copy the per-phase cycle sums of the last run (if enabled) into out, then

@@ -30,7 +30,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <functional>
 #include <memory>
 #include <numeric>
 #include <string>
@@ -483,50 +482,41 @@ __device__ __forceinline__ void stats_small(GRes& r, uint32_t x0, uint32_t x1, u
 
 // Thread-level group of c <= N members starting at a.
 // A sequence's signature flag (process_kmer_set's seqs_with_a_signature.insert,
-// signature_build.tcc:269).  Bit 0 of the pointer selects the form (option flag_bits): a byte per
-// sequence, stored; or a bit per sequence, read first and set by a device-scope atomicOr only while
-// it reads clear (most sequences are flagged by their first kept k-mer, later marks only read; a
-// stale read costs one redundant atomic, never a lost flag).  k_flags_from_bits expands the bits.
-__device__ __forceinline__ void mark_seq(uint8_t* f, uint32_t s) {
-    const uintptr_t p = reinterpret_cast<uintptr_t>(f);
-    if (p & 1u) {
-        uint32_t* w = reinterpret_cast<uint32_t*>(p & ~(uintptr_t)1) + (s >> 5);
-        const uint32_t m = 1u << (s & 31u);
-        if (!(*w & m)) atomicOr(w, m);
-    } else {
-        f[s] = 1;
-    }
+// signature_build.tcc:269): a bit per sequence, read first and set by a device-scope atomicOr only
+// while it reads clear (most sequences are flagged by their first kept k-mer, later marks only
+// read; a stale read costs one redundant atomic, never a lost flag).  k_flags_from_bits expands
+// the bits into the per-sequence bytes of the output.
+__device__ __forceinline__ void mark_seq(uint32_t* f, uint32_t s) {
+    uint32_t* w = f + (s >> 5);
+    const uint32_t m = 1u << (s & 31u);
+    if (!(*w & m)) atomicOr(w, m);
 }
 
 // mark_seq for up to N sequences of one thread (0xFFFFFFFF: none): every flag read issued before
 // the first atomic, so the reads overlap instead of waiting one after another behind the
 // previous mark's atomic (a stale read costs one redundant atomic, never a lost flag)
 template <int N>
-__device__ __forceinline__ void mark_seqs(uint8_t* f, int flag_check, const uint32_t (&s)[N]) {
-    const uintptr_t p = reinterpret_cast<uintptr_t>(f);
-    if (p & 1u) {
-        uint32_t* w = reinterpret_cast<uint32_t*>(p & ~(uintptr_t)1);
-        uint32_t cur[N];
+__device__ __forceinline__ void mark_seqs(uint32_t* w, const uint32_t (&s)[N]) {
+    uint32_t cur[N];
 #pragma unroll
-        for (int u = 0; u < N; ++u) cur[u] = s[u] != 0xFFFFFFFFu ? w[s[u] >> 5] : 0xFFFFFFFFu;
+    for (int u = 0; u < N; ++u) cur[u] = s[u] != 0xFFFFFFFFu ? w[s[u] >> 5] : 0xFFFFFFFFu;
 #pragma unroll
-        for (int u = 0; u < N; ++u) {
-            const uint32_t m = 1u << (s[u] & 31u);
-            if (!(cur[u] & m)) atomicOr(w + (s[u] >> 5), m);
-        }
-    } else {
-        uint8_t cur[N];
-#pragma unroll
-        for (int u = 0; u < N; ++u) cur[u] = s[u] != 0xFFFFFFFFu && flag_check ? f[s[u]] : (uint8_t)(s[u] == 0xFFFFFFFFu);
-#pragma unroll
-        for (int u = 0; u < N; ++u)
-            if (cur[u] == 0) f[s[u]] = 1;
+    for (int u = 0; u < N; ++u) {
+        const uint32_t m = 1u << (s[u] & 31u);
+        if (!(cur[u] & m)) atomicOr(w + (s[u] >> 5), m);
     }
 }
 
+// mark_seqs for eight sequences behind a call: big_group<32> sits on its register cap (168 VGPRs,
+// three waves per SIMD), and with the marks inlined the compiler spills a register there
+struct Seq8 {
+    uint32_t s[8];
+};
+__device__ __attribute__((noinline)) void mark_seqs8(uint32_t* w, Seq8 q) { mark_seqs<8>(w, q.s); }
+
 template <int N, class V>
 __device__ GRes group_thread(const V& v, uint64_t a, uint32_t c, const uint32_t* __restrict__ glen,
-                             uint8_t* __restrict__ flags) {
+                             uint32_t* __restrict__ flags) {
     GRes r;
     r.kept = false;
     uint32_t fn[N], of[N];
@@ -573,7 +563,7 @@ __device__ GRes group_thread(const V& v, uint64_t a, uint32_t c, const uint32_t*
     for (uint32_t t = 0; t < c; ++t) {
         const uint64_t lo = v.lov(a + t);
         const uint32_t s = (uint32_t)(lo >> 36);
-        if (flags) mark_seq(flags, s);
+        mark_seq(flags, s);
         if (t >= rb && t < rb + best_c) {
             const uint32_t len = glen[s];
             sum += len;
@@ -593,7 +583,7 @@ __device__ GRes group_thread(const V& v, uint64_t a, uint32_t c, const uint32_t*
 // has >= 3 members and its median/var are deferred.
 template <class V>
 __device__ GRes group_wave(const V& v, uint64_t a, uint32_t c, const uint32_t* __restrict__ glen,
-                           uint8_t* __restrict__ flags) {
+                           uint32_t* __restrict__ flags) {
     const uint32_t lane = threadIdx.x & 63u;
     GRes r;
     r.kept = false;
@@ -656,7 +646,7 @@ __device__ GRes group_wave(const V& v, uint64_t a, uint32_t c, const uint32_t* _
     uint32_t sum = 0;
     for (uint32_t t = lane; t < c; t += 64) {
         const uint32_t s = (uint32_t)(v.lov(a + t) >> 36);
-        if (flags) mark_seq(flags, s);
+        mark_seq(flags, s);
         if (t >= rb && t < rb + best_c) sum += glen[s];
     }
     sum = wave_sum(sum);
@@ -706,7 +696,7 @@ __device__ __forceinline__ uint32_t wg_min(uint32_t x, uint32_t* s_wave) {
 // false (nothing written) when the group has more than hcap function runs.
 template <class V>
 __device__ bool group_block(const V& v, uint64_t a, uint32_t c, const uint32_t* __restrict__ glen,
-                            uint8_t* __restrict__ flags, uint32_t* heads, uint32_t hcap, uint32_t* s_wave, GRes& r) {
+                            uint32_t* __restrict__ flags, uint32_t* heads, uint32_t hcap, uint32_t* s_wave, GRes& r) {
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
     r.kept = false;
     uint32_t H = 0;
@@ -751,7 +741,7 @@ __device__ bool group_block(const V& v, uint64_t a, uint32_t c, const uint32_t* 
     uint32_t sum = 0;
     for (uint32_t t = tid; t < c; t += nt) {
         const uint32_t s = (uint32_t)(v.lov(a + t) >> 36);
-        if (flags) mark_seq(flags, s);
+        mark_seq(flags, s);
         if (t >= rb && t < rb + best_c) sum += glen[s];
     }
     sum = wg_sum(sum, s_wave);
@@ -1443,13 +1433,10 @@ __device__ __forceinline__ void chains_body(const Job* __restrict__ jobs, const 
                                             const unsigned long long* hi_p, uint64_t cap,
                                             const uint32_t* __restrict__ lens, const uint32_t* __restrict__ recs32,
                                             const uint32_t* __restrict__ tmp32, const uint32_t* __restrict__ big32,
-                                            skm_stored_kmer_data* __restrict__ out, uint32_t max_n,
-                                            unsigned long long* queue) {
+                                            skm_stored_kmer_data* __restrict__ out, uint32_t max_n) {
     // blocks of 64 jobs, one job per lane: the P^2 of a block on an even wave, its variance on an odd
     // one (grid may be smaller than the job count: a capped grid keeps few waves resident beside a
-    // concurrent kernel, longest jobs first).  With `queue` (two zeroed counters) every wave takes
-    // its next block from its half's counter, so a wave held by a block of long chains does not
-    // also own a fixed share of the later blocks; without it, wave pairs stride over the blocks.
+    // concurrent kernel, longest jobs first); wave pairs stride over the blocks.
     const uint64_t lo = lo_p ? (uint64_t)*lo_p : 0ull;
     const uint64_t hi = min((uint64_t)*hi_p, cap);
     if (hi <= lo) return;
@@ -1457,13 +1444,7 @@ __device__ __forceinline__ void chains_body(const Job* __restrict__ jobs, const 
     const uint64_t njobs = hi - lo;
     const bool var_wave = ((threadIdx.x >> 6) & 1u) != 0;
     const uint64_t pairs = (uint64_t)gridDim.x * (blockDim.x >> 7);
-    auto take = [&]() -> uint64_t {
-        uint32_t v = 0;
-        if ((threadIdx.x & 63u) == 0) v = (uint32_t)atomicAdd(queue + (var_wave ? 1 : 0), 1ull);
-        return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-    };
-    for (uint64_t pr = queue ? take() : (uint64_t)blockIdx.x * (blockDim.x >> 7) + (threadIdx.x >> 7); pr * 64 < njobs;
-         pr = queue ? take() : pr + pairs) {
+    for (uint64_t pr = (uint64_t)blockIdx.x * (blockDim.x >> 7) + (threadIdx.x >> 7); pr * 64 < njobs; pr += pairs) {
         const uint64_t j = pr * 64 + (threadIdx.x & 63u);
         if (j >= njobs) break;
         const Job jb = jobs[j];
@@ -1494,15 +1475,13 @@ __global__ __launch_bounds__(256) void k_chains(const Job* __restrict__ jobs, co
                                                 const unsigned long long* hi_p, uint64_t cap,
                                                 const uint32_t* __restrict__ lens, const uint32_t* __restrict__ recs32,
                                                 const uint32_t* __restrict__ tmp32, const uint32_t* __restrict__ big32,
-                                                skm_stored_kmer_data* __restrict__ out, uint32_t max_n = 0,
-                                                unsigned long long* queue = nullptr) {
-    chains_body(jobs, lo_p, hi_p, cap, lens, recs32, tmp32, big32, out, max_n, queue);
+                                                skm_stored_kmer_data* __restrict__ out, uint32_t max_n = 0) {
+    chains_body(jobs, lo_p, hi_p, cap, lens, recs32, tmp32, big32, out, max_n);
 }
 __global__ __launch_bounds__(256) void k_chains_stash(const Job* __restrict__ jobs, const unsigned long long* lo_p,
                                                       const unsigned long long* hi_p, uint64_t cap,
-                                                      skm_stored_kmer_data* __restrict__ out, uint32_t max_n,
-                                                      unsigned long long* queue) {
-    chains_body(jobs, lo_p, hi_p, cap, nullptr, nullptr, nullptr, nullptr, out, max_n, queue);
+                                                      skm_stored_kmer_data* __restrict__ out, uint32_t max_n) {
+    chains_body(jobs, lo_p, hi_p, cap, nullptr, nullptr, nullptr, nullptr, out, max_n);
 }
 
 // Diagnostics: one half of the wave-pair chain code alone (which 0: P^2, 1: variance).
@@ -2560,7 +2539,7 @@ struct BucketArgs {
     int rem_bits;
     const uint32_t* glen;      // protein length by global sequence index (read only for lengths >= 65536
                                // and by overflow sub-buckets)
-    uint8_t* flags;
+    uint32_t* flags;           // signature flag bits by global sequence index (mark_seq)
     unsigned long long* ctr;   // [0] kept [1] overflow entries [2] flagged seqs [3] jobs [4] lens
     uint64_t* out_keys;
     skm_stored_kmer_data* out_data;
@@ -2574,12 +2553,9 @@ struct BucketArgs {
     unsigned long long* big_ctr;  // descriptors reserved in big_desc (the pass's one counter, k_big_groups reads it)
     int prio;                  // wave issue priority of the group-by (above the concurrent chains)
     int pshift;                // KEY_BITS - pass bits (key_h43)
-    int flag_check;            // 1: a signature flag is stored only when it reads 0 (option flag_check)
     const uint32_t* skip;      // k_ovf_plan's verdict for the pass (nonzero: the run is being abandoned)
     uint32_t sub_target;       // k_partition: target elements per level-2 sub-bucket (0: SUB_TARGET)
-    int diag;                  // option diag (diagnostics only)
     const uint32_t* order;     // k_partition: bucket of each workgroup (k_part_order; null: blockIdx.x)
-    int part_class;            // k_partition: 0 all buckets, 1 the oversized ones (order[nb] of them), 2 the rest
 };
 
 #define SKM_STAMP(i)                                                          \
@@ -2767,9 +2743,8 @@ __device__ __forceinline__ void seg_groups(const SubLds& L, uint32_t q0, uint32_
     const uint64_t Rs = R & segmask;
     const uint32_t rs = Rs ? (uint32_t)__ffsll((long long)Rs) - 1u : sbase;
     const uint32_t s = (uint32_t)(key >> ELEM_I_BITS) & ((1u << ELEM_S_BITS) - 1u);
-    const uint32_t fl = (A.flag_check && real && A.flags) ? A.flags[s] : 0u;  // diag 1: no flags
     const uint32_t len = (pay & 1u) ? A.glen[s] : len16;
-    if (kept && real && fl == 0 && A.flags) mark_seq(A.flags, s);
+    if (kept && real) mark_seq(A.flags, s);
     const uint32_t x0 = (uint32_t)__shfl((int)len, (int)(rs + cbest - 1), 64);  // first visited
     const uint32_t x1 = (uint32_t)__shfl((int)len, (int)rs, 64);                // second when cbest == 2
     if (kept && inrun && cbest >= 3) L.lens32[2 * a + (rs + cbest - 1 - lane)] = len;  // visit order
@@ -2888,7 +2863,7 @@ __device__ __forceinline__ uint32_t process_sub(const uint64_t* __restrict__ src
                 L.rank[j] = 0xFFFFu;  // singleton marker
             }
         }
-        if (A.flags) mark_seqs<LPER>(A.flags, A.flag_check, ms);
+        mark_seqs<LPER>(A.flags, ms);
         M = tot >> 13;
         G = tot & 0x1FFFu;
     }
@@ -3203,7 +3178,7 @@ struct BigArgs {
     const uint64_t* tmp_hi;
     const uint64_t* recs_lo;   // lo slots: the members' protein lengths
     const uint64_t* tmp_lo;
-    uint8_t* flags;
+    uint32_t* flags;
     BigOut* out;
 };
 
@@ -3277,15 +3252,20 @@ __device__ __forceinline__ void big_group(const BigArgs& B, uint64_t g, uint64_t
     }
     // the members' flags, up to 8 reads in flight per lane before their atomics (one mark after
     // another waited a global round trip each: E of them per lane)
-    if (B.flags) {
-        constexpr int MC = E < 8 ? E : 8;
+    constexpr int MC = E < 8 ? E : 8;
 #pragma unroll
-        for (int e0 = 0; e0 < E; e0 += MC) {
-            uint32_t ms[MC];
+    for (int e0 = 0; e0 < E; e0 += MC) {
+        uint32_t ms[MC];
 #pragma unroll
-            for (int u = 0; u < MC; ++u)
-                ms[u] = fo[e0 + u] != 0xFFFFFFFFu ? (uint32_t)(ky[e0 + u] >> (16 + ELEM_I_BITS)) : 0xFFFFFFFFu;
-            mark_seqs<MC>(B.flags, 0, ms);
+        for (int u = 0; u < MC; ++u)
+            ms[u] = fo[e0 + u] != 0xFFFFFFFFu ? (uint32_t)(ky[e0 + u] >> (16 + ELEM_I_BITS)) : 0xFFFFFFFFu;
+        if constexpr (E > 16) {
+            Seq8 q;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) q.s[u] = ms[u];
+            mark_seqs8(B.flags, q);
+        } else {
+            mark_seqs<MC>(B.flags, ms);
         }
     }
     uint32_t sum = 0;
@@ -3424,11 +3404,9 @@ __global__ __launch_bounds__(BIG_WG) void k_big_append(const BigOut* __restrict_
 // several ranks): count by the next b2 bits of rem, exclusive scan, scatter into tmp.  Writes the
 // sub-bucket table for k_bucket_process and queues sub-buckets larger than CAP for k_overflow,
 // so the overflow path (and its long P^2 chains) can run concurrently with the group-by.
-// PT_ROUND elements staged per round of the level-2 scatter.  LDS ~52 KB at 2048: three
-// workgroups per CU (the sub-bucket of a staged element is recomputed from its key instead of
-// staged, and the running write offsets double as the sub-bucket table); 4096 (option
-// partition_round = 1, 2): one per CU, but each round's run per sub-bucket is twice as long, so
-// fewer 128-byte lines leave L2 partly written.
+// PT_ROUND elements staged per round of the level-2 scatter.  LDS ~52 KB: three workgroups per CU
+// (the sub-bucket of a staged element is recomputed from its key instead of staged, and the
+// running write offsets double as the sub-bucket table).
 // k_partition's workgroup order: the buckets of more than twice the mean size first, then the rest,
 // each class in bucket order.  One workgroup walks a whole bucket, and a routed heavy k-mer makes
 // its bucket several times the mean (C3: ~1 M occurrences beside a mean of ~230 K): started late in
@@ -3454,8 +3432,9 @@ __global__ __launch_bounds__(1024) void k_part_order(const uint64_t* __restrict_
     if (threadIdx.x == 0) order[nb] = nbig;  // the oversized buckets: order[0, nbig)
 }
 
-template <uint32_t PT_ROUND, uint32_t PT_THREADS, int MINB>
-__global__ __launch_bounds__(PT_THREADS, MINB) void k_partition(BucketArgs A) {
+constexpr uint32_t PT_ROUND = 2048, PT_THREADS = BP_THREADS;
+
+__global__ __launch_bounds__(PT_THREADS, 3) void k_partition(BucketArgs A) {
     __shared__ uint32_t s_cur[(1 << MAX_B2) + 1];   // counts, then running write offsets
     __shared__ uint32_t s_rc[1 << MAX_B2];          // this round's count per sub-bucket
     __shared__ uint16_t s_ro[(1 << MAX_B2) + 1];    // ... and its staging offset (<= PT_ROUND)
@@ -3463,17 +3442,7 @@ __global__ __launch_bounds__(PT_THREADS, MINB) void k_partition(BucketArgs A) {
     __shared__ uint64_t s_sl[PT_ROUND];
     __shared__ __align__(16) uint32_t s_wave[48];
     if (blockIdx.x >= A.nbuckets) return;
-    // part_class 1: the oversized buckets only (order[0, nbig)), 2: the others (order[nbig, nb))
-    uint32_t slot = blockIdx.x;
-    if (A.part_class) {
-        const uint32_t nbig = A.order[A.nbuckets];
-        if (A.part_class == 1 && slot >= nbig) return;
-        if (A.part_class == 2) {
-            slot += nbig;
-            if (slot >= A.nbuckets) return;
-        }
-    }
-    const uint32_t bucket = A.order ? A.order[slot] : slot;
+    const uint32_t bucket = A.order ? A.order[blockIdx.x] : blockIdx.x;
     const uint64_t r0 = A.bstart[bucket], r1 = A.bstart[bucket + 1];
     const uint64_t n = r1 - r0;
     uint32_t* tab = A.sub_tab + (uint64_t)bucket * SUB_TAB;
@@ -3534,22 +3503,17 @@ __global__ __launch_bounds__(PT_THREADS, MINB) void k_partition(BucketArgs A) {
     // sub-bucket's run contiguously (whole lines instead of scattered 8-byte stores)
     // the next round's elements are loaded into registers before this round's LDS work, so the
     // HBM latency overlaps the staging instead of opening every round
-    // (the register prefetch only in the 2048 form: the 4096 form would spill)
     constexpr uint32_t PER = PT_ROUND / PT_THREADS;
-    constexpr bool PF = PER <= 4;
-    constexpr uint32_t NPF = PF ? PER : 1;
     for (uint32_t p = 0; p < nseg; ++p) {
         uint64_t base, len;
         seg(p, base, len);
-        uint64_t nh[NPF], nl[NPF];
-        if constexpr (PF) {
+        uint64_t nh[PER], nl[PER];
 #pragma unroll
-            for (uint32_t u = 0; u < PER; ++u) {
-                const uint64_t j = threadIdx.x + (uint64_t)u * PT_THREADS;
-                if (j < len) {
-                    nh[u] = A.recs_hi[base + j];
-                    nl[u] = A.recs_lo[base + j];
-                }
+        for (uint32_t u = 0; u < PER; ++u) {
+            const uint64_t j = threadIdx.x + (uint64_t)u * PT_THREADS;
+            if (j < len) {
+                nh[u] = A.recs_hi[base + j];
+                nl[u] = A.recs_lo[base + j];
             }
         }
         for (uint64_t rb = 0; rb < len; rb += PT_ROUND) {
@@ -3559,20 +3523,12 @@ __global__ __launch_bounds__(PT_THREADS, MINB) void k_partition(BucketArgs A) {
 #pragma unroll
             for (uint32_t u = 0; u < PER; ++u) {
                 sb[u] = 0xFFFFFFFFu;
-                if constexpr (PF) {
-                    eh[u] = nh[u];
-                    el[u] = nl[u];
-                    const uint64_t j = rb + PT_ROUND + threadIdx.x + (uint64_t)u * PT_THREADS;
-                    if (j < len) {
-                        nh[u] = A.recs_hi[base + j];
-                        nl[u] = A.recs_lo[base + j];
-                    }
-                } else {
-                    const uint64_t j = rb + threadIdx.x + (uint64_t)u * PT_THREADS;
-                    if (j < len) {
-                        eh[u] = A.recs_hi[base + j];
-                        el[u] = A.recs_lo[base + j];
-                    }
+                eh[u] = nh[u];
+                el[u] = nl[u];
+                const uint64_t j = rb + PT_ROUND + threadIdx.x + (uint64_t)u * PT_THREADS;
+                if (j < len) {
+                    nh[u] = A.recs_hi[base + j];
+                    nl[u] = A.recs_lo[base + j];
                 }
             }
             __syncthreads();
@@ -3670,8 +3626,6 @@ __global__ __launch_bounds__(BP_THREADS) void k_overflow(BucketArgs A, OvfScratc
     const uint32_t q_lo = lo_slot < 0 ? 0u : plan[lo_slot], q_hi = plan[hi_slot];
     auto entry = [&](const OvfEntry e) {
         if (e.n == 0) return;  // every key of the sub-bucket went to k_heavy, or k_ovf_light took the rest
-        if ((A.diag & 32) && e.n <= (uint32_t)CAP) return;  // diagnostics: the entries of one LDS chunk
-        if ((A.diag & 64) && e.n > (uint32_t)CAP) return;   //   / of the global network, skipped
         // (after k_ovf_split: the light remainder, compacted to the front of the sub-bucket's range)
         const uint64_t* src_hi = (e.src ? A.tmp_hi : A.recs_hi) + e.off;
         const uint64_t* src_lo = (e.src ? A.tmp_lo : A.recs_lo) + e.off;
@@ -3979,7 +3933,6 @@ struct HeavyArgs {
     // giant chains (>= 2^giant_class samples): samples and jobs in this pass's slot buffers, run
     // by k_chain_dyn on a chain stream as soon as k_heavy ends (the pass's own lens buffer is
     // reused by the next pass; the slot's is not until its chains are done)
-    uint32_t nosort;              // diagnostics (option diag & 2): the samples in member order
     uint32_t fast;                // n_functions <= HV_FT: function counts in LDS, bucketed sample order
     uint32_t n_total;             // sequences of the build (the bucket range of the sequence indices)
     uint32_t giant_min;           // 0: off
@@ -4354,7 +4307,7 @@ __device__ __forceinline__ void wave_sort_desc(uint64_t (&v)[E]) {
 template <int E>
 __device__ __forceinline__ void heavy_bucket_out(const uint32_t* __restrict__ ks, const uint32_t* __restrict__ ls,
                                                  uint32_t a, uint32_t c, uint32_t nb, uint32_t* __restrict__ out,
-                                                 uint8_t* flags) {
+                                                 uint32_t* flags) {
     const uint32_t lane = threadIdx.x & 63u;
     uint64_t v[E];
 #pragma unroll
@@ -4368,7 +4321,7 @@ __device__ __forceinline__ void heavy_bucket_out(const uint32_t* __restrict__ ks
         const uint32_t i = (uint32_t)e * 64u + lane;
         if (i < nb) {
             out[i] = (uint32_t)v[e];
-            if (flags) mark_seq(flags, (uint32_t)(v[e] >> 32) - 1u);
+            mark_seq(flags, (uint32_t)(v[e] >> 32) - 1u);
         }
     }
 }
@@ -4448,7 +4401,7 @@ __global__ __launch_bounds__(HEAVY_WG) void k_heavy(BucketArgs A, HeavyArgs H) {
             uint32_t bm = 0;
             for (uint32_t d = tid; d < NBK; d += nt) bm = max(bm, s_bk[d]);
             bm = wg_max(bm, s_wave);
-            bucketed = bm <= HV_BCAP && !H.nosort;
+            bucketed = bm <= HV_BCAP;
         } else {
             // ---- Boyer-Moore majority function, then its exact count ----
             uint32_t cand = 0xFFFFFFFFu, cc = 0;
@@ -4567,7 +4520,7 @@ __global__ __launch_bounds__(HEAVY_WG) void k_heavy(BucketArgs A, HeavyArgs H) {
                     } else {
                         ks[slot] = 0u;
                         ls[slot] = 0u;
-                        if (A.flags) mark_seq(A.flags, sq);
+                        mark_seq(A.flags, sq);
                     }
                 }
             }
@@ -4622,7 +4575,7 @@ __global__ __launch_bounds__(HEAVY_WG) void k_heavy(BucketArgs A, HeavyArgs H) {
                     const bool v = f[u] != 0xFFFFFFFFu;
                     const uint32_t s = hr_seq(l[u]);
                     const bool best = f[u] == best_f;
-                    if (v && !best && A.flags) mark_seq(A.flags, s);  // the best members' flags go out in sorted order below
+                    if (v && !best) mark_seq(A.flags, s);  // the best members' flags go out in sorted order below
                     wave_hist_add(s_hist, hr_off(l[u]) >> 8, v);
                     if (best) {
                         sum += gl[u];
@@ -4674,7 +4627,7 @@ __global__ __launch_bounds__(HEAVY_WG) void k_heavy(BucketArgs A, HeavyArgs H) {
             // ---- samples in visit order: sequence indices descending ----
             int bits = 0;
             while (bits < 32 && (smax >> bits)) bits += RB;
-            sorted = H.nosort ? sa : wg_radix_sort_u32(sa, sb, cb, bits, s_hist, s_wc, s_run, tag);
+            sorted = wg_radix_sort_u32(sa, sb, cb, bits, s_hist, s_wc, s_run, tag);
             __syncthreads();
         }
         if (tid == 0) {
@@ -4736,7 +4689,7 @@ __global__ __launch_bounds__(HEAVY_WG) void k_heavy(BucketArgs A, HeavyArgs H) {
                         // monotone sequence indices: the length gathers and the signature flags of the
                         // best members touch neighbouring lines instead of random ones
                         lens_out[(uint64_t)loff + t] = A.glen[sv[u]];
-                        if (A.flags) mark_seq(A.flags, sv[u]);
+                        mark_seq(A.flags, sv[u]);
                     }
                 }
             }
@@ -4960,7 +4913,7 @@ __global__ void k_func_hist_seqs(const SeqMeta* __restrict__ meta, uint32_t nseq
             if (s_h[f]) atomicAdd(&swf[f], s_h[f]);
 }
 
-// option flag_bits: the per-sequence bytes from the run's flag bits (one word of 32 flags per thread)
+// the per-sequence bytes from the run's flag bits (one word of 32 flags per thread)
 __global__ void k_flags_from_bits(const uint32_t* __restrict__ bits, uint32_t nseq, uint8_t* __restrict__ flags) {
     for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < (nseq + 31) / 32; w += gridDim.x * blockDim.x) {
         const uint32_t v = bits[w];
@@ -5113,35 +5066,16 @@ struct Tune {
     // tail_async: the 1025..CAP class on a second tail stream.  Measured slower at C3 (round 6,
     // one box: 1445 / 1474 vs 1391 / 1429 ms/step): the concurrent classes slow the chains after them
     int big_split = 0;
-    // tail_async: the tail is issued after the next pass's scan kernels (k_colsum .. k_stage_init),
-    // which otherwise wait ~2 ms per pass behind k_big_groups' persistent grid for their workgroups.
-    // Within noise at C3 (round 6, one box: 1434 / 1387 vs 1414 / 1377 ms/step): the scan's 25 ms
-    // per step go, the tail then slows the staging more
-    int tail_defer = 0;
     int part_order = 1;              // k_partition: the buckets of > 2x the mean size first (k_part_order)
-    // part_order: those buckets by 1024-thread workgroups on stream 2, beside the rest.  Within noise
-    // at C3 (round 6, one box, three alternations: 1353 / 1378 / 1378 vs 1374 / 1371 / 1353 ms/step):
-    // the heavy buckets' workgroups stay as long, now beside the rest
-    int part_split = 0;
-    // tail_async: the split writes the pass's elements into one of two element buffers by pass
-    // parity, so the next pass's split no longer waits for this pass's tail (which reads them);
-    // the wait moves to the partition.  Costs 16 B per element of the largest pass (when it fits
-    // beside a kept arena of a quarter of the valid windows).  With tail_defer, within noise at C3
-    // (1396 / 1405 vs 1414 / 1377 ms/step): the device is busy either way, the tail's work moves
-    int recs_rot = 0;
     int emit_group = 0;              // key-range passes emitted per residue scan (0: 4; 1, 2, 4, 8 or 16)
     int route_first = -1;
     int route_first_min = 1 << 17;   // route_first: k-mers of >= this many occurrences make pass 0 (C3: ~4.5 %
                                      //   of the windows; those of >= 2^14 hold ~17 %, too many for a short pass)
     int route_heavy_min = 1 << 14;   // key-range passes: k-mers of >= this many occurrences are routed into
                                      //   the first half of the passes (0: off; k_pass_ids)
-    int overlap = 0;                 // key-range passes, one GPU: pipelined passes (a second element set)
     int chain_cus = 0;               // CUs of the long-chain stream (0: all; set_option recreates it)
     int side_cus = 0;                // CUs of the overflow and selection streams (0: all)
     int serial_overflow = 0;         // diagnostics: 1 = the overflow path starts after the group-by kernel
-    int flag_check = 0;              // 1: k_bucket_process reads a signature flag before storing it
-    int partition_round = 0;         // k_partition staging rounds: 0 = 2048 elements (three 512-thread
-                                     //   workgroups per CU), 1 = 4096 (one), 2 = 4096 (one of 1024 threads)
     int stage_round = 1;             // key-range passes: 1 = the staged position scatter in half rounds
                                      //   (2048 elements, four workgroups per CU); 0 = full rounds
     // key-range passes: stashed long chains below this many samples run one lane each (k_chains,
@@ -5150,18 +5084,11 @@ struct Tune {
     // whole batch, and a k_bucket_process workgroup needs half of a CU's registers and LDS
     int lane_long = 1 << 20;
     int lane_grid = 256;             //   their k_chains grid
-    int chain_queue = 0;             // k_chains: waves take 64-job blocks from a queue (0: strided)
     int lane_streams = 1;            //   the streams their batches rotate over (1..4)
     int lane_tail = 1 << 16;         //   the last batch's threshold (its wave pairs are the tail's latency)
     int sub_target = 0;              // k_partition's target elements per level-2 sub-bucket (0: SUB_TARGET)
     int heavy_lsd = 0;               // 1: k_heavy's round-3 path (Boyer-Moore + recount, LSD sort, length
                                      //   gathers) for every key instead of the one-read bucketed path
-    int flag_bits = 1;               // signature flags as bits, read before an atomic set (mark_seq);
-                                     //   0: a byte store per kept occurrence (C3: +58 ms/step)
-    int diag = 0;                    // diagnostics only (wrong results): 1 = no signature flag stores,
-                                     //   2 = k_heavy without its sequence-index sort, 4 = no chain kernels,
-                                     //   8 = no stashed long chains, 16 = no per-pass k_chains,
-                                     //   32 / 64 = k_overflow skips its entries of <= / > CAP elements
     int handoff_index_limit = 0;     // tests: finish hand-offs of >= this many k-mers take u64 arena
                                      //   indices (0: 2^32, where they are needed)
     int handoff_max_chunk = 0;       // tests: cap on the hand-off's chunk size (0: memory-planned)
@@ -5237,8 +5164,6 @@ struct skm_build {
     DevBuf d_part_order;                // k_part_order's workgroup -> bucket map
     DevBuf d_cur0, d_cur1, d_slices;   // staged scatter cursors
     DevBuf d_flagbits;
-    DevBuf d_chainq;              // k_chains work queues: two counters per launch of a run
-    uint32_t chainq_next = 0;
     DevBuf d_keys, d_data, d_ctr, d_flags, d_dfunc, d_swf, d_ovf, d_ovf_hi, d_ovf_lo, d_ovf_heads, d_ovf_job, d_ovf_fm;
     DevBuf d_jobs, d_lens, d_stamps, d_big_desc, d_big_out;
     uint64_t big_cap = 0, n_big = 0, big_kept = 0;
@@ -5275,11 +5200,8 @@ struct skm_build {
     hipStream_t stream_tail2 = nullptr; //   the groups of 1025..CAP members beside the smaller big groups
     hipEvent_t ev_tail_bp = nullptr, ev_tail_done = nullptr, ev_tail2 = nullptr;
     bool tail_pending = false;          // the last pass's tail is still in flight on stream_tail
-    std::function<void()> tail_issue;   // tail_defer: the last pass's tail, not yet issued
-    hipEvent_t ev_scan = nullptr;       // tail_defer: the next pass's scan kernels are done
-    bool rot = false;                   // recs_rot: odd passes split into d_recs_*2
     uint64_t free_after_prepare = 0;    // device bytes free after prepare (counters [44])
-    hipEvent_t ev_part = nullptr, ev_split = nullptr, ev_part_heavy = nullptr, ev_light = nullptr;
+    hipEvent_t ev_part = nullptr, ev_split = nullptr, ev_light = nullptr;
     DevBuf d_hv_keys, d_hv_rec, d_hv_len, d_hv_s0, d_hv_s1;   // heavy keys of the split overflow
     DevBuf d_sub_tab, d_jobs2, d_jobs3;
 
@@ -5325,15 +5247,6 @@ struct skm_build {
     uint32_t sel_wg = SEL_WG;            // k_pass_ids / k_pass_emit workgroups (tally rows)
     hipStream_t stx = nullptr;
     hipEvent_t ev_staged = nullptr, ev_emit = nullptr;
-    // pipelined passes (option overlap, one GPU, key-range passes): a second element buffer set,
-    // so that a pass's overflow path (streams 2/3, reading its buffers) overlaps the next pass's
-    // extract / split / partition instead of closing the pass; per-set counter blocks, plans and
-    // overflow lists; ev_ovf_done[k] = the overflow path (and the pass accounting) of the last
-    // pass that used set k is complete, ev_main_done[k] = its main-stream work is
-    bool overlap = false;
-    DevBuf d_recs_hi2, d_recs_lo2, d_tmp_hi2, d_tmp_lo2, d_ovf2b;
-    hipEvent_t ev_ovf_done[2] = {}, ev_main_done[2] = {};
-    bool ovf_pending[2] = {false, false};
     int64_t emit_q = -1;                // the group whose scan is queued on stx
     uint32_t pf_nwg = 1;                // count-kernel rows of the histogram matrix (pass mode)
     uint64_t pf_span = 0;
@@ -5799,7 +5712,7 @@ void prepare_local(skm_build* b) {
     b->d_bstart32.ensure(sizeof(uint32_t) * (NB + 1));
     b->d_bstart.ensure(sizeof(uint64_t) * (NB + 1));
     b->d_owner_start.ensure(sizeof(uint64_t) * 80);
-    b->d_ctr.ensure(3 * 256);
+    b->d_ctr.ensure(2 * 256);
     b->d_dfunc.ensure(sizeof(uint32_t) * std::max<uint32_t>(b->opts.n_functions, 1));
     b->d_swf.ensure(sizeof(uint32_t) * std::max<uint32_t>(b->opts.n_functions, 1));
 }
@@ -5876,7 +5789,7 @@ void size_passes(skm_build* b, int forced_pb = -1) {
 }
 
 // buffers sized by the number of elements this rank groups in one pass
-bool tail_async_on(const skm_build* b) { return b->tune.tail_async && b->world == 1 && b->pass_bits && !b->overlap; }
+bool tail_async_on(const skm_build* b) { return b->tune.tail_async && b->world == 1 && b->pass_bits; }
 
 void ensure_local(skm_build* b, uint64_t n) {
     if (tail_async_on(b)) {  // within PASS_BYTES: the 16 B/element of the received set (world > 1) are free
@@ -6230,45 +6143,9 @@ void prepare(const Ranks& bs) {
             b->long_cap = b->pass_bits ? b->valid_total / 8 + (1u << 16) : 0;
         }
         alloc_caps(b);
-        // recs_rot: the second element buffer, before the kept arena takes the rest of the memory
-        b->rot = false;
-        if (b->tune.recs_rot && b->tune.tail_async && !b->tune.overlap && b->world == 1 && b->pass_bits > 0) {
-            const uint64_t W = std::max<uint64_t>(b->pass_max, 1);
-            if (b->d_recs_hi2.bytes >= 8 * W && b->d_recs_lo2.bytes >= 8 * W) {
-                b->rot = true;
-            } else {
-                size_t fr = 0, tot = 0;
-                SKM_HIP(hipMemGetInfo(&fr, &tot));
-                const uint64_t held = (uint64_t)b->d_keys.bytes + (uint64_t)b->d_data.bytes;
-                const uint64_t need = 16 * W + 32 * W + (1ull << 30) + 18 * (b->valid_total / 4);
-                if ((uint64_t)fr + held > need) {
-                    b->d_recs_hi2.ensure(8 * W);
-                    b->d_recs_lo2.ensure(8 * W);
-                    b->rot = true;
-                }
-            }
-        }
         size_arena(b);
         b->d_flags.ensure(std::max<uint64_t>(b->n_total, 1));
         b->d_flagbits.ensure(4 * ((b->n_total + 31) / 32 + 1));
-        // pipelined passes when the second element buffer set fits beside everything else with a
-        // tenth of the memory to spare (the data-sized buffers may still grow on a redo)
-        b->overlap = false;
-        if (b->tune.overlap && b->world == 1 && b->pass_bits > 0) {
-            size_t fr = 0, tot = 0;
-            SKM_HIP(hipMemGetInfo(&fr, &tot));
-            const uint64_t need = 16 * std::max<uint64_t>(b->pass_max, 1) + 16 * b->cap_local;
-            if (b->d_recs_hi2.bytes >= 8 * std::max<uint64_t>(b->pass_max, 1) && b->d_tmp_hi2.bytes >= 8 * b->cap_local) {
-                b->overlap = true;
-            } else if ((uint64_t)fr > need + tot / 10) {
-                b->d_recs_hi2.ensure(8 * std::max<uint64_t>(b->pass_max, 1));
-                b->d_recs_lo2.ensure(8 * std::max<uint64_t>(b->pass_max, 1));
-                b->d_tmp_hi2.ensure(8 * b->cap_local);
-                b->d_tmp_lo2.ensure(8 * b->cap_local);
-                b->overlap = true;
-            }
-            if (b->overlap) b->d_ovf2b.ensure(sizeof(OvfEntry) * std::max<uint64_t>(b->ovf_cap, 1));
-        }
         {
             size_t fr = 0, tot = 0;
             SKM_HIP(hipMemGetInfo(&fr, &tot));
@@ -6315,35 +6192,13 @@ void emit_group(skm_build* b, uint32_t g, hipStream_t st) {
     if (st != b->stream) SKM_HIP(hipEventRecord(b->ev_emit, st));
 }
 
-// the element buffer set, counter block, plan and overflow list of a pass (set 0 unless overlap)
-inline int pset(const skm_build* b, uint32_t pass) { return b->overlap ? (int)(pass & 1u) : 0; }
-inline bool rset(const skm_build* b, uint32_t pass) { return pset(b, pass) || (b->rot && (pass & 1u)); }
-inline uint64_t* recs_hi(skm_build* b, uint32_t pass) { return (rset(b, pass) ? b->d_recs_hi2 : b->d_recs_hi).as<uint64_t>(); }
-inline uint64_t* recs_lo(skm_build* b, uint32_t pass) { return (rset(b, pass) ? b->d_recs_lo2 : b->d_recs_lo).as<uint64_t>(); }
-inline uint64_t* tmp_hi(skm_build* b, uint32_t pass) { return (pset(b, pass) ? b->d_tmp_hi2 : b->d_tmp_hi).as<uint64_t>(); }
-inline uint64_t* tmp_lo(skm_build* b, uint32_t pass) { return (pset(b, pass) ? b->d_tmp_lo2 : b->d_tmp_lo).as<uint64_t>(); }
-// d_ctr: [0] the kept arena cursor, [2] the flag count (run-level); per-set pass counters at 32, 64
-inline unsigned long long* pass_ctr(skm_build* b, uint32_t pass) {
-    return b->d_ctr.as<unsigned long long>() + 32 * (1 + pset(b, pass));
-}
+// d_ctr: [0] the kept arena cursor, [2] the flag count (run-level); the pass counters at 32
+inline unsigned long long* pass_ctr(skm_build* b) { return b->d_ctr.as<unsigned long long>() + 32; }
 
 // the main stream waits for the previous pass's tail (tail_async) before it overwrites what the tail
 // reads (the split's recs, then the partition's tmp, the counters, the job lists) or reads what it
 // writes (the stash cursors, the kept arena's totals)
-// tail_defer: the last pass's tail is issued now (after_scan: behind the next pass's scan kernels)
-void issue_tail(skm_build* b, bool after_scan) {
-    if (!b->tail_issue) return;
-    if (after_scan) {
-        SKM_HIP(hipEventRecord(b->ev_scan, b->stream));
-        SKM_HIP(hipStreamWaitEvent(b->stream_tail, b->ev_scan, 0));
-    }
-    std::function<void()> f;
-    f.swap(b->tail_issue);
-    f();
-}
-
 void join_tail(skm_build* b) {
-    issue_tail(b, false);
     if (!b->tail_pending) return;
     SKM_HIP(hipStreamWaitEvent(b->stream, b->ev_tail_done, 0));
     b->tail_pending = false;
@@ -6373,8 +6228,8 @@ void phase_extract(skm_build* b, uint32_t pass) {
     X.blk2seq = b->d_blk2seq.as<uint32_t>();
     X.meta = b->d_meta.as<SeqMeta>();
     X.s_base = b->s_base;
-    X.out_hi = recs_hi(b, pass);
-    X.out_lo = recs_lo(b, pass);
+    X.out_hi = b->d_recs_hi.as<uint64_t>();
+    X.out_lo = b->d_recs_lo.as<uint64_t>();
     uint32_t nwg = b->nwg, hist_rows = b->nwg;
     if (b->pass_bits) {
         // this pass's window positions and histogram: its group's scan, queued on stx during the
@@ -6410,22 +6265,17 @@ void phase_extract(skm_build* b, uint32_t pass) {
     SKM_HIP(hipGetLastError());
     SKM_HIP(hipEventRecord(b->ev[2], st));
     // ---- 3. scatter: 64-way staged pass into tmp, then the split into the final buckets ----
-    if (b->overlap && b->ovf_pending[pset(b, pass)]) {  // the set's previous pass still read it
-        SKM_HIP(hipStreamWaitEvent(st, b->ev_ovf_done[pset(b, pass)], 0));
-        b->ovf_pending[pset(b, pass)] = false;
-    }
     const int l0_shift = nbits - SC_L0_BITS;
     b->d_cur0.ensure(8ull * 64 * CUR_STRIDE);
     b->d_cur1.ensure(8ull * NB * CUR_STRIDE);
     b->d_slices.ensure(4 * 80);
     SKM_LAUNCH(b, k_stage_init, dim3((NB + 255) / 256), dim3(256), 0, st, b->d_bstart.as<uint64_t>(), NB, l0_shift,
                        b->d_cur0.as<unsigned long long>(), b->d_cur1.as<unsigned long long>(), b->d_slices.as<uint32_t>());
-    issue_tail(b, true);
     // the level-0 staging: tmp, or (tail_async) a buffer of its own, so it overlaps the previous
     // pass's tail, which still reads tmp and recs
     const bool sep = tail_async_on(b);
-    uint64_t* stg_hi = sep ? b->d_stg_hi.as<uint64_t>() : tmp_hi(b, pass);
-    uint64_t* stg_lo = sep ? b->d_stg_lo.as<uint64_t>() : tmp_lo(b, pass);
+    uint64_t* stg_hi = (sep ? b->d_stg_hi : b->d_tmp_hi).as<uint64_t>();
+    uint64_t* stg_lo = (sep ? b->d_stg_lo : b->d_tmp_lo).as<uint64_t>();
     if (!sep) join_tail(b);
     if (b->pass_bits && b->tune.stage_round == 1)
         SKM_LAUNCH_AS(b, "k_extract_stage_pos", (k_extract_stage_pos<SC_ROUND_HALF, 4>), dim3(nwg), dim3(EX_THREADS), 0, st, X,
@@ -6442,12 +6292,11 @@ void phase_extract(skm_build* b, uint32_t pass) {
     else
         SKM_LAUNCH(b, k_extract_stage, dim3(nwg), dim3(EX_THREADS), 0, st, X, b->d_cur0.as<unsigned long long>(),
                            stg_hi, stg_lo);
-    // recs_rot: the split writes the other element buffer; the wait moves to the partition
-    if (!b->rot) join_tail(b);
+    join_tail(b);  // the split overwrites the element buffer the previous pass's tail reads
     const uint32_t nsl = (uint32_t)(ceil_div(b->pass_max, SC_SLICE) + (1u << SC_L0_BITS));
     SKM_LAUNCH(b, k_split_stage, dim3(nsl), dim3(EX_THREADS), 0, st, stg_hi,
                        stg_lo, b->d_bstart.as<uint64_t>(), nbits, b->d_slices.as<uint32_t>(),
-                       b->d_cur1.as<unsigned long long>(), recs_hi(b, pass), recs_lo(b, pass));
+                       b->d_cur1.as<unsigned long long>(), b->d_recs_hi.as<uint64_t>(), b->d_recs_lo.as<uint64_t>());
     SKM_HIP(hipGetLastError());
     SKM_HIP(hipEventRecord(b->ev[3], st));
 }
@@ -6599,17 +6448,6 @@ int giant_class(const skm_build* b) {
 constexpr uint32_t JOB_NWG = 256;      // k_job_count / k_job_scatter workgroups (one chunk each)
 constexpr uint32_t LONG_GRID = 2048;   // k_chain_long / k_long_stash workgroups (one job at a time)
 
-constexpr uint32_t CHAINQ_SLOTS = 256;  // k_chains launches per run (2 per pass + the stash batches)
-
-// a zeroed pair of k_chains queue counters on stream st (distinct per launch of the run)
-unsigned long long* chain_queue(skm_build* b, hipStream_t st) {
-    if (!b->tune.chain_queue) return nullptr;
-    b->d_chainq.ensure(16ull * CHAINQ_SLOTS);
-    unsigned long long* q = b->d_chainq.as<unsigned long long>() + 2 * (b->chainq_next++ % CHAINQ_SLOTS);
-    SKM_HIP(hipMemsetAsync(q, 0, 16, st));
-    return q;
-}
-
 void launch_chains(skm_build* b, hipStream_t st, const Job* jobs, const unsigned long long* nj_d, uint64_t cap,
                    ChainSet& cs, const uint32_t* lens, const uint32_t* recs32, const uint32_t* tmp32,
                    const uint32_t* big32, skm_stored_kmer_data* out, uint32_t long_class,
@@ -6624,7 +6462,6 @@ void launch_chains(skm_build* b, hipStream_t st, const Job* jobs, const unsigned
     // k_job_scan leaves the long jobs' count after the offsets; they lead the sorted order
     const uint64_t* nlong_d = cs.offs.as<uint64_t>() + (uint64_t)JOB_NWG * JOB_CLASSES;
     const auto* nlong_u = reinterpret_cast<const unsigned long long*>(nlong_d);
-    const bool run_chains = !(tn.diag & 4) && !(tn.diag & 16);
     if (b->pass_bits == 0) {
         // one pass: the long chains start on st as soon as their jobs are sorted
         const uint32_t lds = (uint32_t)tn.chain_lds_kb * 1024u;
@@ -6634,9 +6471,8 @@ void launch_chains(skm_build* b, hipStream_t st, const Job* jobs, const unsigned
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             attr = true;
         }
-        if (run_chains)
-            SKM_LAUNCH(b, k_chain_long, dim3(LONG_GRID), dim3(128), lds, st, cs.sorted.as<Job>(), nullptr, nlong_u,
-                       lens, recs32, tmp32, big32, out, tn.chain_prio);
+        SKM_LAUNCH(b, k_chain_long, dim3(LONG_GRID), dim3(128), lds, st, cs.sorted.as<Job>(), nullptr, nlong_u,
+                   lens, recs32, tmp32, big32, out, tn.chain_prio);
     } else {
         SKM_LAUNCH(b, k_long_plan, dim3(1), dim3(1024), 0, st, cs.sorted.as<Job>(), nlong_d,
                            cs.long_off.as<uint64_t>(), b->d_run.as<unsigned long long>(), b->long_cap,
@@ -6651,11 +6487,8 @@ void launch_chains(skm_build* b, hipStream_t st, const Job* jobs, const unsigned
         SKM_HIP(hipStreamWaitEvent(st_short, ev_sorted, 0));
         ss = st_short;
     }
-    if (run_chains) {
-        unsigned long long* q = chain_queue(b, ss);
-        SKM_LAUNCH(b, k_chains, dim3(max_wgs ? max_wgs : (uint32_t)std::max(1, tn.chain_grid)), dim3(256), 0, ss,
-                   cs.sorted.as<Job>(), nlong_u, nj_d, cap, lens, recs32, tmp32, big32, out, 0u, q);
-    }
+    SKM_LAUNCH(b, k_chains, dim3(max_wgs ? max_wgs : (uint32_t)std::max(1, tn.chain_grid)), dim3(256), 0, ss,
+               cs.sorted.as<Job>(), nlong_u, nj_d, cap, lens, recs32, tmp32, big32, out, 0u);
     SKM_HIP(hipGetLastError());
 }
 
@@ -6667,21 +6500,22 @@ void phase_group(skm_build* b, uint32_t pass) {
     hipStream_t st = b->stream, st2 = b->stream2, st3 = b->stream3;
     const bool multi = b->world > 1;
     const uint32_t NB1 = 1u << b->b1_bits;
-    join_tail(b);  // recs_rot: the previous pass's tail still read tmp, the counters and the job lists
+    // if the previous pass's tail is still pending (the split joins it, so today it never is), it
+    // still reads tmp, the counters and the job lists, all written from here on
+    join_tail(b);
     SKM_HIP(hipEventRecord(b->ev[4], st));
     // per-pass counters; [0] (kept k-mers: the arena cursor) and the signature flags run over
     // all passes (begin_run clears them)
-    unsigned long long* ctr_d = pass_ctr(b, pass);
+    unsigned long long* ctr_d = pass_ctr(b);
     SKM_HIP(hipMemsetAsync(ctr_d, 0, 256, st));
     unsigned long long* run_d = b->d_run.as<unsigned long long>();
-    const int ks = pset(b, pass);
-    uint32_t* plan_d = b->d_plan.as<uint32_t>() + PLAN_SLOTS * ks;
-    OvfEntry* ovf2_d = (ks ? b->d_ovf2b : b->d_ovf2).as<OvfEntry>();
+    uint32_t* plan_d = b->d_plan.as<uint32_t>();
+    OvfEntry* ovf2_d = b->d_ovf2.as<OvfEntry>();
     BucketArgs A;
-    A.recs_hi = multi ? b->d_rhi.as<uint64_t>() : recs_hi(b, pass);
-    A.recs_lo = multi ? b->d_rlo.as<uint64_t>() : recs_lo(b, pass);
-    A.tmp_hi = tmp_hi(b, pass);
-    A.tmp_lo = tmp_lo(b, pass);
+    A.recs_hi = (multi ? b->d_rhi : b->d_recs_hi).as<uint64_t>();
+    A.recs_lo = (multi ? b->d_rlo : b->d_recs_lo).as<uint64_t>();
+    A.tmp_hi = b->d_tmp_hi.as<uint64_t>();
+    A.tmp_lo = b->d_tmp_lo.as<uint64_t>();
     A.bstart = multi ? b->d_vstart.as<uint64_t>() : b->d_bstart.as<uint64_t>();
     A.seg_start = multi ? b->d_seg_start.as<uint64_t>() : nullptr;
     A.seg_len = multi ? b->d_seg_len.as<uint32_t>() : nullptr;
@@ -6693,10 +6527,7 @@ void phase_group(skm_build* b, uint32_t pass) {
     A.rem_bits = KEY_BITS - b->pass_bits - b->owner_bits - b->b1_bits;
     A.pshift = KEY_BITS - b->pass_bits;
     A.glen = b->d_glen.as<uint32_t>();
-    A.flags = (b->tune.diag & 1) ? nullptr
-              : b->tune.flag_bits ? reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(b->d_flagbits.p) | 1u)
-                                  : b->d_flags.as<uint8_t>();
-    A.flag_check = b->tune.flag_bits ? 0 : b->tune.flag_check;  // reads the byte form only
+    A.flags = b->d_flagbits.as<uint32_t>();
     A.ctr = ctr_d;
     A.out_keys = b->d_keys.as<uint64_t>();
     A.out_data = b->d_data.as<skm_stored_kmer_data>();
@@ -6711,39 +6542,18 @@ void phase_group(skm_build* b, uint32_t pass) {
     A.big_ctr = ctr_d + 5;
     A.skip = nullptr;
     A.sub_target = (uint32_t)std::max(0, b->tune.sub_target);
-    A.diag = b->tune.diag;
     if (b->stamps) {
         SKM_HIP(hipMemsetAsync(b->d_stamps.p, 0, 32 * 8, st));
         A.stamps = b->d_stamps.as<unsigned long long>();
     }
     // ---- 4a. level-2 partition (the oversized buckets' workgroups first) ----
     A.order = nullptr;
-    A.part_class = 0;
     if (b->tune.part_order) {
         b->d_part_order.ensure(4ull * (NB1 + 1));
         SKM_LAUNCH(b, k_part_order, dim3(1), dim3(1024), 0, st, A.bstart, NB1, b->d_part_order.as<uint32_t>());
         A.order = b->d_part_order.as<uint32_t>();
     }
-    if (A.order && b->tune.part_split && b->tune.partition_round == 0 && !b->overlap) {
-        // part_split: the oversized buckets on stream 2 by 1024-thread workgroups (rounds of 4096),
-        // beside the others on the main stream -- a heavy bucket's workgroup no longer sets the
-        // kernel's length (stream 2's earlier work is joined: the split waited for the last tail)
-        BucketArgs AH = A;
-        AH.part_class = 1;
-        SKM_HIP(hipEventRecord(b->ev_part, st));
-        SKM_HIP(hipStreamWaitEvent(st2, b->ev_part, 0));
-        SKM_LAUNCH_AS(b, "k_partition", (k_partition<4096, 1024, 1>), dim3(NB1), dim3(1024), 0, st2, AH);
-        SKM_HIP(hipEventRecord(b->ev_part_heavy, st2));
-        A.part_class = 2;
-        SKM_LAUNCH_AS(b, "k_partition", (k_partition<2048, BP_THREADS, 3>), dim3(NB1), dim3(BP_THREADS), 0, st, A);
-        SKM_HIP(hipStreamWaitEvent(st, b->ev_part_heavy, 0));
-        A.part_class = 0;
-    } else if (b->tune.partition_round == 1)
-        SKM_LAUNCH_AS(b, "k_partition", (k_partition<4096, 512, 1>), dim3(NB1), dim3(512), 0, st, A);
-    else if (b->tune.partition_round == 2)
-        SKM_LAUNCH_AS(b, "k_partition", (k_partition<4096, 1024, 1>), dim3(NB1), dim3(1024), 0, st, A);
-    else
-        SKM_LAUNCH_AS(b, "k_partition", (k_partition<2048, BP_THREADS, 3>), dim3(NB1), dim3(BP_THREADS), 0, st, A);
+    SKM_LAUNCH(b, k_partition, dim3(NB1), dim3(BP_THREADS), 0, st, A);
     SKM_HIP(hipGetLastError());
     SKM_HIP(hipEventRecord(b->ev[10], st));
     // the group's position slots are free once its last pass has staged its elements; the next
@@ -6807,7 +6617,6 @@ void phase_group(skm_build* b, uint32_t pass) {
     H.len = b->d_hv_len.as<uint32_t>();
     H.s0 = b->d_hv_s0.as<uint32_t>();
     H.s1 = b->d_hv_s1.as<uint32_t>();
-    H.nosort = (b->tune.diag & 2) ? 1u : 0u;
     H.fast = b->opts.n_functions <= HV_FT && !b->tune.heavy_lsd ? 1u : 0u;
     H.n_total = std::max<uint32_t>(b->n_total, 1);
     // giant chains: samples and jobs in this pass's own buffers, run on a rotating chain stream
@@ -6906,8 +6715,16 @@ void phase_group(skm_build* b, uint32_t pass) {
         SKM_HIP(hipEventRecord(b->ev_tail_bp, st));
         SKM_HIP(hipStreamWaitEvent(tt, b->ev_tail_bp, 0));
     }
-    hipEvent_t* ev = b->ev;  // this pass's events (the deferred tail is issued after use_evset(pass + 1))
-    auto big_tail = [=]() {
+    // ---- 6. deferred P^2 / variance chains: the overflow's as soon as both parts are grouped
+    //      (the long ones on stream 2, the per-lane ones on stream 3), the group-by's on st ----
+    SKM_HIP(hipEventRecord(b->ev_o3[0], st3));
+    SKM_HIP(hipStreamWaitEvent(st2, b->ev_o3[0], 0));
+    // (k_ovf_light's jobs keep their lengths in tmp, like the group-by's)
+    launch_chains(b, st2, A2.jobs, ctr_d + 8 + 3, b->jobs2_cap, b->cs_ovf, A2.lens, reinterpret_cast<const uint32_t*>(A.recs_hi),
+                  reinterpret_cast<const uint32_t*>(A.tmp_hi), nullptr, A.out_data, (uint32_t)b->tune.ovf_long_class, st3, b->ev_o3[2], (uint32_t)b->tune.ovf_chain_wgs);
+    SKM_HIP(hipEventRecord(b->ev_o[2], st2));
+    SKM_HIP(hipEventRecord(b->ev_o3[1], st3));
+    // ---- the tail: the big groups, then the group-by's chains ----
     // k_ovf_light's groups of > 64 members are in the descriptor list too (in the default timeline
     // it ends long before the group-by does)
     if (light) SKM_HIP(hipStreamWaitEvent(tt, b->ev_light, 0));
@@ -6927,65 +6744,21 @@ void phase_group(skm_build* b, uint32_t pass) {
     }
     SKM_LAUNCH(b, k_big_append, dim3(256), dim3(BIG_WG), 0, tt, BA.out, BA, A);
     SKM_HIP(hipGetLastError());
-    SKM_HIP(hipEventRecord(ev[12], tt));
-    };
-    // ---- 6. deferred P^2 / variance chains: the overflow's as soon as both parts are grouped
-    //      (the long ones on stream 2, the per-lane ones on stream 3), the group-by's on st ----
-    SKM_HIP(hipEventRecord(b->ev_o3[0], st3));
-    SKM_HIP(hipStreamWaitEvent(st2, b->ev_o3[0], 0));
-    // (k_ovf_light's jobs keep their lengths in tmp, like the group-by's)
-    launch_chains(b, st2, A2.jobs, ctr_d + 8 + 3, b->jobs2_cap, b->cs_ovf, A2.lens, reinterpret_cast<const uint32_t*>(A.recs_hi),
-                  reinterpret_cast<const uint32_t*>(A.tmp_hi), nullptr, A.out_data, (uint32_t)b->tune.ovf_long_class, st3, b->ev_o3[2], (uint32_t)b->tune.ovf_chain_wgs);
-    SKM_HIP(hipEventRecord(b->ev_o[2], st2));
-    SKM_HIP(hipEventRecord(b->ev_o3[1], st3));
-    hipEvent_t* ev_o = b->ev_o;
-    hipEvent_t* ev_o3 = b->ev_o3;
-    auto main_tail = [=]() {
-    big_tail();
+    SKM_HIP(hipEventRecord(b->ev[12], tt));
     launch_chains(b, tt, A.jobs, ctr_d + 3, b->jobs_cap, b->cs_main, A.lens, reinterpret_cast<const uint32_t*>(A.recs_hi),
                   reinterpret_cast<const uint32_t*>(A.tmp_hi), nullptr, A.out_data, (uint32_t)b->tune.main_long_class);
-    if (b->overlap) {
-        // the pass ends on the main stream here; its overflow path and accounting finish on
-        // stream 2 beside the next pass, whose staging into this set waits for ev_ovf_done
-        SKM_HIP(hipEventRecord(b->ev_main_done[ks], st));
-        SKM_HIP(hipEventRecord(ev[6], st));
-        SKM_HIP(hipStreamWaitEvent(st2, ev_o3[1], 0));
-        SKM_HIP(hipStreamWaitEvent(st2, b->ev_main_done[ks], 0));
-        SKM_LAUNCH(b, k_pass_account, dim3(1), dim3(1), 0, st2, ctr_d, run_d, b->jobs_cap, b->jobs2_cap, b->big_cap,
-                   b->lens_cap);
-        SKM_HIP(hipGetLastError());
-        SKM_HIP(hipEventRecord(b->ev_ovf_done[ks], st2));
-        b->ovf_pending[ks] = true;
-        SKM_HIP(hipEventRecord(ev[7], st));
-        return;
-    }
-    SKM_HIP(hipStreamWaitEvent(tt, ev_o[2], 0));
-    SKM_HIP(hipStreamWaitEvent(tt, ev_o3[1], 0));
-    SKM_HIP(hipEventRecord(ev[6], tt));
+    SKM_HIP(hipStreamWaitEvent(tt, b->ev_o[2], 0));
+    SKM_HIP(hipStreamWaitEvent(tt, b->ev_o3[1], 0));
+    SKM_HIP(hipEventRecord(b->ev[6], tt));
     // ---- 7. run totals and the chain lists' bounds ----
     SKM_LAUNCH(b, k_pass_account, dim3(1), dim3(1), 0, tt, ctr_d, run_d, b->jobs_cap, b->jobs2_cap, b->big_cap,
                        b->lens_cap);
     SKM_HIP(hipGetLastError());
-    SKM_HIP(hipEventRecord(ev[7], tt));
+    SKM_HIP(hipEventRecord(b->ev[7], tt));
     if (tail_async) {
         SKM_HIP(hipEventRecord(b->ev_tail_done, tt));
         b->tail_pending = true;
     }
-    };
-    // tail_defer: issued by the next pass's phase_extract after its scan kernels (or by join_tail)
-    if (tail_async && b->tune.tail_defer && pass + 1 < NP && !b->overlap)
-        b->tail_issue = main_tail;
-    else
-        main_tail();
-}
-
-// overlap: the main stream waits for every pass's overflow path still in flight
-void drain_overflow(skm_build* b) {
-    for (int k = 0; k < 2; ++k)
-        if (b->ovf_pending[k]) {
-            SKM_HIP(hipStreamWaitEvent(b->stream, b->ev_ovf_done[k], 0));
-            b->ovf_pending[k] = false;
-        }
 }
 
 // Work buffers whose size depends on the data (the overflow scratch, the split path, the chain
@@ -7008,8 +6781,7 @@ void alloc_caps(skm_build* b) {
     b->d_hv_s0.ensure(4 * Sp);
     b->d_hv_s1.ensure(4 * Sp);
     b->d_ovf2.ensure(sizeof(OvfEntry) * std::max<uint64_t>(b->ovf_cap, 1));
-    if (b->overlap) b->d_ovf2b.ensure(sizeof(OvfEntry) * std::max<uint64_t>(b->ovf_cap, 1));
-    b->d_plan.ensure(4 * PLAN_SLOTS * 2);
+    b->d_plan.ensure(4 * PLAN_SLOTS);
     b->d_run.ensure(8 * RUN_SLOTS);
     b->d_sub_tab.ensure(4ull * (1u << b->b1_bits) * SUB_TAB);
     b->d_stamps.ensure(32 * 8);
@@ -7051,17 +6823,14 @@ void alloc_caps(skm_build* b) {
 void begin_run(skm_build* b) {
     hipStream_t st = b->stream;
     alloc_caps(b);
-    b->chainq_next = 0;
     b->emit_q = -1;  // no pass group's positions are queued from an earlier (possibly aborted) run
     b->giant_timed = false;
     b->tail_pending = false;
-    b->tail_issue = nullptr;
     SKM_HIP(hipEventRecord(b->ev_start, st));
-    SKM_HIP(hipMemsetAsync(b->d_ctr.p, 0, 3 * 256, st));
-    b->ovf_pending[0] = b->ovf_pending[1] = false;
+    SKM_HIP(hipMemsetAsync(b->d_ctr.p, 0, 2 * 256, st));
     SKM_HIP(hipMemsetAsync(b->d_run.p, 0, 8 * RUN_SLOTS, st));
     SKM_HIP(hipMemsetAsync(b->d_flags.p, 0, b->n_total ? b->n_total : 1, st));
-    if (b->tune.flag_bits) SKM_HIP(hipMemsetAsync(b->d_flagbits.p, 0, 4 * ((b->n_total + 31) / 32 + 1), st));
+    SKM_HIP(hipMemsetAsync(b->d_flagbits.p, 0, 4 * ((b->n_total + 31) / 32 + 1), st));
     b->d_gstat.ensure(16);
     SKM_HIP(hipMemsetAsync(b->d_gstat.p, 0, 16, st));
     if (b->tune.poison_jobs && b->pass_bits && b->long_jobs_cap)
@@ -7152,20 +6921,18 @@ void flush_long_chains(skm_build* b, int slot) {
     const bool few = (1 << b->pass_bits) < 8;
     const int lmax = slot < 16 && !few ? b->tune.lane_long : std::min(b->tune.lane_long, b->tune.lane_tail);
     const uint32_t lane_max = lmax > 0 ? (uint32_t)lmax : 0u;
-    if (!(b->tune.diag & 4) && !(b->tune.diag & 8))
-        SKM_LAUNCH(b, k_chain_long, dim3(LONG_GRID), dim3(128), 0, cs, b->d_long_jobs.as<Job>(), rng, rng + 1,
-                   nullptr, nullptr, nullptr, nullptr, b->d_data.as<skm_stored_kmer_data>(), b->tune.chain_prio,
-                   lane_max);
-    if (lane_max && !(b->tune.diag & 4) && !(b->tune.diag & 8)) {
+    SKM_LAUNCH(b, k_chain_long, dim3(LONG_GRID), dim3(128), 0, cs, b->d_long_jobs.as<Job>(), rng, rng + 1,
+               nullptr, nullptr, nullptr, nullptr, b->d_data.as<skm_stored_kmer_data>(), b->tune.chain_prio,
+               lane_max);
+    if (lane_max) {
         // a batch lasts as long as its longest chain: batches rotate over lane_streams streams so a
         // batch of giant chains does not hold back the next one
         const int ls = slot % std::max(1, std::min(b->tune.lane_streams, (int)skm_build::LANE_ST));
         hipStream_t lst = b->lane_st[ls];
         SKM_HIP(hipStreamWaitEvent(lst, b->chain_ev[0], 0));
-        unsigned long long* q = chain_queue(b, lst);
         SKM_LAUNCH(b, k_chains_stash, dim3((uint32_t)std::max(1, b->tune.lane_grid)), dim3(256), 0, lst,
                    b->d_long_jobs.as<Job>(), rng, rng + 1, b->long_jobs_cap, b->d_data.as<skm_stored_kmer_data>(),
-                   lane_max, q);
+                   lane_max);
         b->lane_used[ls] = true;
     }
     SKM_HIP(hipGetLastError());
@@ -7177,8 +6944,7 @@ void phase_stats(skm_build* b) {
     const uint32_t F = b->opts.n_functions;
     SKM_HIP(hipEventRecord(b->ev_tail[0], st));  // the last pass is issued: the tail starts here
     join_tail(b);
-    drain_overflow(b);
-    if (b->tune.flag_bits && b->n_total)
+    if (b->n_total)
         SKM_LAUNCH(b, k_flags_from_bits, dim3(1024), dim3(256), 0, st, b->d_flagbits.as<uint32_t>(),
                    (uint32_t)b->n_total, b->d_flags.as<uint8_t>());
     // the arena's keys decoded and distinct_functions counted while the last chains run: neither
@@ -7304,7 +7070,6 @@ void run_once(const Ranks& bs) {
             const uint32_t nb = std::min<uint32_t>(P >= 2 ? std::min<uint32_t>(P, (uint32_t)std::max(1, b->tune.chain_batches)) : 1u, 16u);
             const uint32_t per = std::max<uint32_t>(1u, P / nb);
             if (nb > 1 && (pass + 1) % per == 0 && pass + 1 < P) {
-                drain_overflow(b);  // the snapshot takes every stash issued so far, complete
                 flush_long_chains(b, (int)((pass + 1) / per - 1));
             }
         }
@@ -7394,7 +7159,6 @@ int skm_build_create(skm_build** out, const int* devices, int n_devices, const s
     SKM_HIP(hipEventCreateWithFlags(&b->ev_tail2, hipEventDisableTiming));
     SKM_HIP(hipEventCreateWithFlags(&b->ev_tail_bp, hipEventDisableTiming));
     SKM_HIP(hipEventCreateWithFlags(&b->ev_tail_done, hipEventDisableTiming));
-    SKM_HIP(hipEventCreateWithFlags(&b->ev_scan, hipEventDisableTiming));
     use_evset(b, 0);
     SKM_HIP(hipEventCreate(&b->ev_start));
     SKM_HIP(hipStreamCreateWithFlags(&b->chain_st, hipStreamNonBlocking));
@@ -7412,11 +7176,6 @@ int skm_build_create(skm_build** out, const int* devices, int n_devices, const s
     }
     for (auto& e : b->chain_ev) SKM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     SKM_HIP(hipEventCreateWithFlags(&b->ev_part, hipEventDisableTiming));
-    SKM_HIP(hipEventCreateWithFlags(&b->ev_part_heavy, hipEventDisableTiming));
-    for (int k = 0; k < 2; ++k) {
-        SKM_HIP(hipEventCreateWithFlags(&b->ev_ovf_done[k], hipEventDisableTiming));
-        SKM_HIP(hipEventCreateWithFlags(&b->ev_main_done[k], hipEventDisableTiming));
-    }
     for (auto& e : b->ev_tail) SKM_HIP(hipEventCreate(&e));
     for (auto& e : b->ev_giant) SKM_HIP(hipEventCreate(&e));
     for (int i = 0; i < 2; ++i) {
@@ -7779,29 +7538,20 @@ int skm_build_set_option(skm_build* b, const char* name, int64_t value) {
                : n == "poison_jobs" ? &t.poison_jobs
                : n == "route_heavy_min" ? &t.route_heavy_min
                : n == "stage_round" ? &t.stage_round
-               : n == "partition_round" ? &t.partition_round
-               : n == "flag_check" ? &t.flag_check
-               : n == "diag" ? &t.diag
-               : n == "flag_bits" ? &t.flag_bits
+               : n == "serial_overflow" ? &t.serial_overflow
+               : n == "big_split" ? &t.big_split
                : n == "sub_target" ? &t.sub_target
                : n == "lane_long" ? &t.lane_long
                : n == "lane_grid" ? &t.lane_grid
                : n == "lane_tail" ? &t.lane_tail
                : n == "lane_streams" ? &t.lane_streams
-               : n == "chain_queue" ? &t.chain_queue
-               : n == "serial_overflow" ? &t.serial_overflow
-               : n == "overlap" ? &t.overlap
                : n == "heavy_grid" ? &t.heavy_grid
                : n == "route_vacate" ? &t.route_vacate
                : n == "route_first" ? &t.route_first
                : n == "tail_async" ? &t.tail_async
                : n == "big_grid" ? &t.big_grid
                : n == "big_grid_large" ? &t.big_grid_large
-               : n == "big_split" ? &t.big_split
-               : n == "tail_defer" ? &t.tail_defer
                : n == "part_order" ? &t.part_order
-               : n == "part_split" ? &t.part_split
-               : n == "recs_rot" ? &t.recs_rot
                : n == "emit_group" ? &t.emit_group
                : n == "handoff_index_limit" ? &t.handoff_index_limit
                : n == "handoff_max_chunk" ? &t.handoff_max_chunk
@@ -7955,7 +7705,7 @@ int skm_build_counters(skm_build* b, uint64_t* out, int cap) {
                             (uint64_t)(1e3 * b->handoff.sort_ms), (uint64_t)(1e3 * b->handoff.gather_ms),
                             (uint64_t)(1e3 * b->handoff.d2h_ms), b->handoff.max_chunk,
                             (uint64_t)b->handoff.wide_index, b->kept_cap, b->free_after_prepare,
-                            (uint64_t)b->rot, b->ovf_light_sub, b->ovf_light_elems};
+                            0ull /* [45] reserved */, b->ovf_light_sub, b->ovf_light_elems};
     int n = std::min(cap, 48);
     for (int i = 0; i < n; ++i) out[i] = v[i];
     return n;
@@ -8191,17 +7941,16 @@ int skm_build_signature_flags(skm_build* b, uint8_t* out, uint64_t cap) {
 // d_dfunc, d_swf) and the signature flags (d_flags) -- once nothing of the run is in flight
 static void release_work(skm_build* b) {
     SKM_HIP(hipDeviceSynchronize());
-    b->tail_issue = nullptr;
     DevBuf* work[] = {
         &b->d_res, &b->d_meta, &b->d_blk2seq, &b->d_glen, &b->d_hist, &b->d_offs, &b->d_partial, &b->d_rbbase,
         &b->d_bstart32, &b->d_bstart, &b->d_owner_start, &b->d_recs_hi, &b->d_recs_lo, &b->d_tmp_hi, &b->d_tmp_lo,
         &b->d_stg_hi, &b->d_stg_lo, &b->d_part_order, &b->d_cur0, &b->d_cur1, &b->d_slices, &b->d_flagbits,
-        &b->d_chainq, &b->d_ovf, &b->d_ovf_hi, &b->d_ovf_lo, &b->d_ovf_heads, &b->d_ovf_job, &b->d_ovf_fm, &b->d_jobs,
+        &b->d_ovf, &b->d_ovf_hi, &b->d_ovf_lo, &b->d_ovf_heads, &b->d_ovf_job, &b->d_ovf_fm, &b->d_jobs,
         &b->d_lens, &b->d_stamps, &b->d_big_desc, &b->d_big_out, &b->d_rhi, &b->d_rlo, &b->d_cnt_send, &b->d_cnt_recv,
         &b->d_seg_start, &b->d_seg_len, &b->d_vstart, &b->d_xs, &b->d_hv_keys, &b->d_hv_rec, &b->d_hv_len, &b->d_hv_s0,
         &b->d_hv_s1, &b->d_sub_tab, &b->d_jobs2, &b->d_jobs3, &b->d_ids, &b->d_bloom, &b->d_posg, &b->d_histg,
-        &b->d_npos, &b->d_selrows, &b->d_seloff, &b->d_recs_hi2, &b->d_recs_lo2, &b->d_tmp_hi2, &b->d_tmp_lo2,
-        &b->d_ovf2b, &b->d_gstat, &b->d_long_arena, &b->d_long_jobs, &b->d_ovf2, &b->d_plan, &b->d_run};
+        &b->d_npos, &b->d_selrows, &b->d_seloff, &b->d_gstat, &b->d_long_arena, &b->d_long_jobs, &b->d_ovf2, &b->d_plan,
+        &b->d_run};
     for (DevBuf* d : work) d->release();
     for (ChainSet* cs : {&b->cs_main, &b->cs_ovf, &b->cs_ovf3})
         for (DevBuf* d : {&cs->hist, &cs->offs, &cs->sorted, &cs->long_off}) d->release();
@@ -8258,11 +8007,6 @@ void skm_build_destroy(skm_build* b) {
             if (e) (void)hipEventDestroy(e);
     }
     if (b->ev_part) (void)hipEventDestroy(b->ev_part);
-    if (b->ev_part_heavy) (void)hipEventDestroy(b->ev_part_heavy);
-    for (int k = 0; k < 2; ++k) {
-        if (b->ev_ovf_done[k]) (void)hipEventDestroy(b->ev_ovf_done[k]);
-        if (b->ev_main_done[k]) (void)hipEventDestroy(b->ev_main_done[k]);
-    }
     for (auto& e : b->ev_tail)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : b->ev_giant)
@@ -8313,7 +8057,6 @@ void skm_build_destroy(skm_build* b) {
     if (b->ev_tail2) (void)hipEventDestroy(b->ev_tail2);
     if (b->ev_tail_bp) (void)hipEventDestroy(b->ev_tail_bp);
     if (b->ev_tail_done) (void)hipEventDestroy(b->ev_tail_done);
-    if (b->ev_scan) (void)hipEventDestroy(b->ev_scan);
     delete b;
 }
 

@@ -83,30 +83,28 @@ def test_overflow_inline_chains(skm, gpu, inline_min):
     assert_same(got, ref)
 
 
-@pytest.mark.parametrize("passes,long_class,opts", [(1, 6, {}), (2, 14, {}), (4, 8, {}), (64, 14, {}),
-                                                   (4, 8, {"stage_round": 0}), (4, 8, {"partition_round": 1}),
-                                                   (4, 8, {"partition_round": 2}), (1, 6, {"flag_check": 1, "flag_bits": 0}), (4, 8, {"flag_bits": 0}),
-                                                   (4, 8, {"serial_overflow": 1}), (4, 8, {"chain_cus": 32}),
-                                                   (4, 8, {"side_cus": 64}),
-                                                   (4, 8, {"overlap": 1}), (16, 8, {"overlap": 1}),
-                                                   (4, 8, {"overlap": 1, "serial_overflow": 1}),
-                                                   (4, 8, {"lane_long": 0}), (16, 8, {"lane_long": 600}),
-                                                   (16, 8, {"tail_defer": 1, "recs_rot": 1}), (4, 8, {"recs_rot": 1}),
-                                                   (16, 8, {"big_split": 1, "emit_group": 16}),
-                                                   (16, 8, {"part_order": 0}), (16, 8, {"part_split": 0})])
+def _row(passes, long_class, opts, n):
+    # an explicit id, so that a row keeps its id when rows before it come or go
+    return pytest.param(passes, long_class, opts, id=f"{passes}-{long_class}-opts{n}")
+
+
+@pytest.mark.parametrize("passes,long_class,opts", [_row(1, 6, {}, 0), _row(2, 14, {}, 1), _row(4, 8, {}, 2),
+                                                   _row(64, 14, {}, 3), _row(4, 8, {"stage_round": 0}, 4),
+                                                   _row(4, 8, {"serial_overflow": 1}, 9), _row(4, 8, {"chain_cus": 32}, 10),
+                                                   _row(4, 8, {"side_cus": 64}, 11),
+                                                   _row(4, 8, {"lane_long": 0}, 15), _row(16, 8, {"lane_long": 600}, 16),
+                                                   _row(16, 8, {"big_split": 1, "emit_group": 16}, 19),
+                                                   _row(16, 8, {"part_order": 0}, 20), _row(16, 8, {}, 21)])
 def test_key_range_passes(skm, gpu, passes, long_class, opts):
     """Out-of-core build: P passes over disjoint k-mer ranges (each k-mer in exactly one pass)
     give the single-pass result bit for bit, overflow sub-buckets and chains included, and a
     second run over the same handle repeats it (arena cursor, flags and counters reset).  Low
     long-chain classes send most chains through the stash + chain streams that outlive a pass.
-    opts: the staging / partition round-size variants (stage_round 0: full rounds;
-    partition_round 1, 2: rounds of 4096 with 512 / 1024 threads), flag_check, serial_overflow, chain_cus / side_cus (the long-chain / overflow
-    and selection streams on a subset of the CUs), overlap 1 (pipelined passes: a second element
-    buffer set, the pass's overflow path beside the next pass), lane_long 0 / 600 (every stashed long
-    chain on a wave pair / the ones of >= 600 samples: the others one lane each, k_chains),
-    tail_defer / recs_rot (the pass tail issued after the next pass's scan; the split alternating two
-    element buffers), big_split with emit_group 16 (one residue scan for all 16 passes), part_order 0
-    / part_split 0 (k_partition in bucket order / the oversized buckets not split off to stream 2)."""
+    opts: stage_round 0 (full staging rounds), serial_overflow, chain_cus / side_cus (the long-chain
+    / overflow and selection streams on a subset of the CUs), lane_long 0 / 600 (every stashed long
+    chain on a wave pair / the ones of >= 600 samples: the others one lane each, k_chains), big_split
+    with emit_group 16 (one residue scan for all 16 passes), part_order 0 (k_partition in bucket
+    order), and the defaults at 16 passes (the tail_async schedule that C3 runs)."""
     p = synth.generate_arrays(60000, 60, per_file=2000, seed=6)
     r, o, l, f, i, funcs = synth.build_inputs(p)
     ref = oracle_ref.build(r, o, l, f, i, len(funcs))
@@ -125,8 +123,23 @@ def test_key_range_passes(skm, gpu, passes, long_class, opts):
     b.close()
     assert_same(got, ref)
     assert c1["overflow_subbuckets"] > 0 and c1["grouped"] == oracle_ref.count_windows(l, f) - _invalid(r, o, l, f)
-    if opts.get("recs_rot") and passes > 1:
-        assert c1["recs_rot"] == 1  # the second element buffer fits at this size
+
+
+def test_removed_options_are_unknown(skm, gpu):
+    """The schedule variants that were measured and not kept (DESIGN.md sections 4 and 7) are no
+    longer options: each name is refused like any unknown one, and the builder still builds."""
+    p = synth.generate_arrays(300, 12, per_file=100, seed=9)
+    r, o, l, f, i, funcs = synth.build_inputs(p)
+    b = skm.SignatureBuilder(len(funcs))
+    for name in ("overlap", "recs_rot", "tail_defer", "part_split", "partition_round", "flag_bits", "flag_check",
+                 "chain_queue", "diag"):
+        with pytest.raises(skm.SkmError, match="unknown build option"):
+            b.set_option(name, 1)
+    b.add_batch(r, o, l, f, i)
+    got = b.finish()
+    b.close()
+    assert len(got.keys) > 0
+    assert_same(got, oracle_ref.build(r, o, l, f, i, len(funcs)))
 
 
 @pytest.mark.parametrize("passes,route_min,vacate", [(4, 256, 0), (16, 64, 0), (64, 1024, 0), (16, 64, 4), (16, 64, 1),
