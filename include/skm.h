@@ -169,6 +169,10 @@ int skm_build_kernel_timings(skm_build* b, char* names, size_t names_cap, float*
  * the heavy k-mers are split off, at most 2048 occurrences) was grouped by the LDS hash path
  * (k_ovf_light) instead of the overflow sort, [47] the occurrences in them (both 0 with
  * "ovf_light" 0; their kept k-mers count in [8], those of their groups of > 64 members in [10]);
+ * [48] (bucket, part) tasks of the group-by's queue that held a batch (k_bucket_process: a bucket
+ * is eight parts of its level-2 sub-buckets, or one task when it is grouped unpartitioned), [49]
+ * the LDS batches (process_sub calls) they made; both totals over the passes of the run, and both
+ * fixed by the input and the pass count, not by the schedule;
  * returns entries written. */
 int skm_build_counters(skm_build* b, uint64_t* out, int cap);
 /* Host transport: the rank collectives of a multi-process build run by the caller on host

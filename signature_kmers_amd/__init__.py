@@ -366,8 +366,8 @@ class SignatureBuilder:
         return self.counters()["passes"]
 
     def counters(self) -> dict:
-        v = (C.c_uint64 * 48)()
-        n = lib().skm_build_counters(self._h, v, 48)
+        v = (C.c_uint64 * 50)()
+        n = lib().skm_build_counters(self._h, v, 50)
         names = ["windows", "kept", "overflow_subbuckets", "chain_jobs", "chain_samples", "sequences", "grouped",
                  "overflow_elements", "overflow_kept", "big_groups", "big_kept", "passes", "valid", "giant_chains",
                  "giant_max", "redone", "cap_overflow_scratch", "cap_split", "cap_long_samples", "cap_long_jobs",
@@ -376,7 +376,8 @@ class SignatureBuilder:
                  "pass_groups", "add_pack_us", "add_dma_wait_us", "finish_us", "finish_wait_us", "finish_copy_us",
                  "finish_chunks", "finish_select_dev_us", "finish_sort_dev_us", "finish_gather_dev_us",
                  "finish_d2h_dev_us", "finish_max_chunk", "finish_wide_index", "kept_cap",
-                 "free_after_prepare", "recs_rot", "overflow_light_subbuckets", "overflow_light_elements"]
+                 "free_after_prepare", "recs_rot", "overflow_light_subbuckets", "overflow_light_elements",
+                 "groupby_tasks", "groupby_batches"]
         return {names[i]: int(v[i]) for i in range(n)}
 
     def debug_jobs(self, k: int = 64) -> list:

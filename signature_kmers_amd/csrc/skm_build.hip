@@ -6,11 +6,12 @@
 //
 // Device pipeline (one GPU; the multi-GPU form inserts an RCCL all-to-all between 3 and 4):
 //   1. k_extract<count>   residues -> per-workgroup histogram of level-1 buckets (LDS atomics)
-//   2. k_colsum/k_bstart/k_coloffs   exclusive scan of the [workgroup][bucket] matrix
+//   2. k_colsum/k_bstart/k_coloffs   exclusive scan of the [workgroup][bucket] matrix (with key-range
+//                         passes: k_pass_starts, per emission group, from each pass's histogram row)
 //   3. k_extract<scatter> residues -> 16-byte occurrence elements (SoA hi/lo, see make_elem),
 //                         partitioned by level-1 bucket (owner-major)
-//   4. k_bucket_process   one workgroup per level-1 bucket: level-2 partition in HBM, then per
-//                         sub-bucket LDS hash grouping, cut, statistics (short P^2/variance
+//   4. k_bucket_process   persistent workgroups over (level-1 bucket, part) tasks: level-2 partition in
+//                         HBM (k_partition), then per sub-bucket LDS hash grouping, cut, statistics (short P^2/variance
 //                         chains inline, long ones deferred as jobs), compaction of kept k-mers
 //   5. k_overflow         sub-buckets larger than LDS: global-memory bitonic sort + the same
 //                         group processing
@@ -761,6 +762,8 @@ enum : uint32_t {
     RUN_LONG_CUR = 1,       // stashed long-chain samples (run arena cursor)
     RUN_LONG_N = 2,         // stashed long jobs
     RUN_LONG_FLUSHED = 3,   // long jobs already handed to k_chain_long
+    RUN_ACC_BPK_TASKS = 4,  // run totals: the group-by's (bucket, part) tasks that had a batch,
+    RUN_ACC_BPK_BATCHES = 5, //   and the group-by's process_sub batches ([6], [7], [27] are free)
     RUN_SNAP = 28,          // [28..61] k_long_snap ranges, one per stashed-chain batch (<= 17)
     RUN_DEM_TOT = 8,        // demands (max over passes): overflow scratch elements,
     RUN_DEM_SPLIT = 9,      //   split-path elements,
@@ -2540,7 +2543,9 @@ struct BucketArgs {
     const uint32_t* glen;      // protein length by global sequence index (read only for lengths >= 65536
                                // and by overflow sub-buckets)
     uint32_t* flags;           // signature flag bits by global sequence index (mark_seq)
-    unsigned long long* ctr;   // [0] kept [1] overflow entries [2] flagged seqs [3] jobs [4] lens
+    unsigned long long* ctr;   // [0] kept [1] overflow entries [2] flagged seqs [3] jobs [4] lens [5] big-group
+                               // descriptors [6] kept big groups; of the pass's block also [7] k_bucket_process's
+                               // task queue, [13] its tasks with a batch, [15] its batches (CTR_BPK_*)
     uint64_t* out_keys;
     skm_stored_kmer_data* out_data;
     Job* jobs;
@@ -3084,71 +3089,107 @@ __device__ __forceinline__ SubLds sub_lds(SubMem& m) {
     return L;
 }
 
+// Persistent: the grid is two workgroups per CU (what fits), and every workgroup takes (bucket, part)
+// tasks from a counter of the pass's counter block until none is left.  Task t is part t % BPK_PARTS
+// of bucket t / BPK_PARTS: the sub-buckets [c nsub / PARTS, (c + 1) nsub / PARTS) of k_partition's
+// table (nsub is a power of two; below PARTS some parts are empty).  A bucket that is grouped in
+// place (it fits LDS and came from one rank) is its part 0.  A workgroup holds its CU slot from the
+// launch to the end of the queue: with one workgroup per bucket the side streams' grids took the
+// slots of the workgroups that ended, and the group-by ran on half of its slots for half of its
+// time.  A batch never crosses a part boundary, so each part ends with a
+// partly filled batch: at most PARTS - 1 more batches than the ~110 of a whole C3 bucket.
+constexpr uint32_t BPK_PARTS = 8;      // not tuned: 4 and 16 were not measured
+static_assert(BPK_PARTS >= 1 && (BPK_PARTS & (BPK_PARTS - 1)) == 0 && BPK_PARTS <= (1u << MAX_B2), "parts: a power of two");
+constexpr int CTR_BPK_TASK = 7;        // pass counter slot: the next task of k_bucket_process's queue
+constexpr int CTR_BPK_TASKS = 13;      // ... tasks of the pass that had a batch (tests: more than the grid)
+constexpr int CTR_BPK_BATCHES = 15;    // ... process_sub batches of the pass (the parts' packing loss)
+
 __global__ __launch_bounds__(BPK_THREADS, BPK_WAVES_EU) void k_bucket_process(BucketArgs A) {
     static_assert(CAP % BPK_THREADS == 0, "emit assigns CAP / BPK_THREADS elements per thread");
     __shared__ SubMem s_mem;
-    __shared__ uint32_t s_sub[(1 << MAX_B2) + 1];
+    __shared__ uint32_t s_sub[(1 << MAX_B2) / BPK_PARTS + 1];
+    __shared__ uint32_t s_task;
     if (A.skip && *A.skip) return;
     SubLds L = sub_lds(s_mem);
-
-    const uint32_t bucket = blockIdx.x;
-    if (bucket >= A.nbuckets) return;
-    const uint64_t r0 = A.bstart[bucket], r1 = A.bstart[bucket + 1];
-    const uint64_t n = r1 - r0;
-    if (n == 0) return;
-    const uint64_t hprefix = (uint64_t)(A.bucket_base + bucket) << A.rem_bits;
     if (A.prio == 1) __builtin_amdgcn_s_setprio(1);
     if (A.prio == 2) __builtin_amdgcn_s_setprio(2);
     if (A.prio >= 3) __builtin_amdgcn_s_setprio(3);
+    const uint32_t ntasks = A.nbuckets * BPK_PARTS;
+    uint32_t worked = 0, batches = 0;  // tasks of this workgroup that had a batch; its batches
+    for (;;) {
+        if (threadIdx.x == 0) s_task = (uint32_t)atomicAdd(&A.ctr[CTR_BPK_TASK], 1ull);
+        __syncthreads();
+        const uint32_t task = s_task;
+        __syncthreads();  // every thread has read s_task (and is done with the last task's s_sub)
+        if (task >= ntasks) break;
+        const uint32_t bucket = task / BPK_PARTS, part = task % BPK_PARTS;
+        const uint64_t r0 = A.bstart[bucket], r1 = A.bstart[bucket + 1];
+        const uint64_t n = r1 - r0;
+        if (n == 0) continue;
+        const uint64_t hprefix = (uint64_t)(A.bucket_base + bucket) << A.rem_bits;
 
-    // a bucket that fits LDS is one batch straight from recs; otherwise the sub-buckets of the
-    // partition pass (k_partition) in tmp: consecutive sub-buckets are contiguous and hold
-    // disjoint keys, so as many as fit in LDS form one batch (the per-pass fixed costs -- load
-    // latency, barriers, reservations -- are paid once per ~CAP elements).  One call site of
-    // process_sub keeps the kernel's code footprint small.
-    const bool direct = n <= (uint64_t)CAP && A.nsrc == 1;
-    uint32_t nsub = 1;
-    if (!direct) {
-        const uint32_t* tab = A.sub_tab + (uint64_t)bucket * SUB_TAB;
-        nsub = tab[0];
-        for (uint32_t d = threadIdx.x; d <= nsub; d += blockDim.x) s_sub[d] = tab[1 + d];
-        __syncthreads();
-        SKM_STAMP(9);
-    }
-    // batches: the whole bucket (fits LDS), or runs of consecutive sub-buckets of <= CAP elements
-    // in total (sub-buckets beyond CAP are k_overflow's)
-    struct Batch {
-        uint32_t a, cnt;  // first element (bucket-relative), elements; cnt == 0: none left
-    };
-    auto next_batch = [&](uint32_t& d) -> Batch {
+        // a bucket that fits LDS is one batch (k_partition's copy of it); otherwise the sub-buckets of
+        // the partition pass (k_partition) in tmp: consecutive sub-buckets are contiguous and hold
+        // disjoint keys, so as many as fit in LDS form one batch (the per-pass fixed costs -- load
+        // latency, barriers, reservations -- are paid once per ~CAP elements).  One call site of
+        // process_sub keeps the kernel's code footprint small.
+        const bool direct = n <= (uint64_t)CAP && A.nsrc == 1;
+        uint32_t nsub = 1;  // the part's sub-buckets: s_sub[0 .. nsub]
         if (direct) {
-            if (d >= 1) return Batch{0, 0};
-            d = 1;
-            return Batch{0, (uint32_t)n};
+            if (part) continue;
+        } else {
+            const uint32_t* tab = A.sub_tab + (uint64_t)bucket * SUB_TAB;
+            const uint32_t all = tab[0];
+            const uint32_t d0 = (uint32_t)((uint64_t)part * all / BPK_PARTS), d1 = (uint32_t)((uint64_t)(part + 1) * all / BPK_PARTS);
+            if (d0 == d1) continue;
+            nsub = d1 - d0;
+            for (uint32_t d = threadIdx.x; d <= nsub; d += blockDim.x) s_sub[d] = tab[1 + d0 + d];
+            __syncthreads();
+            SKM_STAMP(9);
         }
-        while (d < nsub) {
-            const uint32_t a = s_sub[d];
-            if (s_sub[d + 1] - a == 0 || s_sub[d + 1] - a > (uint32_t)CAP) {  // empty, or k_overflow's
-                ++d;
-                continue;
+        // batches: the whole bucket (fits LDS), or runs of consecutive sub-buckets of <= CAP elements
+        // in total (sub-buckets beyond CAP are k_overflow's)
+        struct Batch {
+            uint32_t a, cnt;  // first element (bucket-relative), elements; cnt == 0: none left
+        };
+        auto next_batch = [&](uint32_t& d) -> Batch {
+            if (direct) {
+                if (d >= 1) return Batch{0, 0};
+                d = 1;
+                return Batch{0, (uint32_t)n};
             }
-            uint32_t d2 = d + 1;
-            while (d2 < nsub && s_sub[d2 + 1] - a <= (uint32_t)CAP) ++d2;
-            d = d2;
-            return Batch{a, s_sub[d2] - a};
+            while (d < nsub) {
+                const uint32_t a = s_sub[d];
+                if (s_sub[d + 1] - a == 0 || s_sub[d + 1] - a > (uint32_t)CAP) {  // empty, or k_overflow's
+                    ++d;
+                    continue;
+                }
+                uint32_t d2 = d + 1;
+                while (d2 < nsub && s_sub[d2 + 1] - a <= (uint32_t)CAP) ++d2;
+                d = d2;
+                return Batch{a, s_sub[d2] - a};
+            }
+            return Batch{0, 0};
+        };
+        // (a bucket that fits LDS was copied to tmp unpartitioned: nothing after k_partition reads recs)
+        const uint64_t* base_hi = A.tmp_hi + r0;
+        const uint64_t* base_lo = A.tmp_lo + r0;
+        const uint64_t sel = LENS_IN_TMP;
+        uint32_t d = 0, nb = 0;
+        for (Batch cur = next_batch(d); cur.cnt; cur = next_batch(d)) {
+            L.lens_sel = (sel << LENS_SEL_SHIFT) | (2 * (r0 + cur.a));
+            L.lens32 = reinterpret_cast<uint32_t*>(const_cast<uint64_t*>(base_hi + cur.a));
+            process_sub(base_hi + cur.a, base_lo + cur.a, cur.cnt, A, hprefix, L);
+            __syncthreads();
+            SKM_STAMP(10);
+            ++nb;
         }
-        return Batch{0, 0};
-    };
-    const uint64_t* base_hi = direct ? A.recs_hi + r0 : A.tmp_hi + r0;
-    const uint64_t* base_lo = direct ? A.recs_lo + r0 : A.tmp_lo + r0;
-    const uint64_t sel = direct ? LENS_IN_RECS : LENS_IN_TMP;
-    uint32_t d = 0;
-    for (Batch cur = next_batch(d); cur.cnt; cur = next_batch(d)) {
-        L.lens_sel = (sel << LENS_SEL_SHIFT) | (2 * (r0 + cur.a));
-        L.lens32 = reinterpret_cast<uint32_t*>(const_cast<uint64_t*>(base_hi + cur.a));
-        process_sub(base_hi + cur.a, base_lo + cur.a, cur.cnt, A, hprefix, L);
-        __syncthreads();
-        SKM_STAMP(10);
+        worked += nb ? 1u : 0u;
+        batches += nb;
+    }
+    if (threadIdx.x == 0 && worked) {
+        atomicAdd(&A.ctr[CTR_BPK_TASKS], (unsigned long long)worked);
+        atomicAdd(&A.ctr[CTR_BPK_BATCHES], (unsigned long long)batches);
     }
 }
 
@@ -3432,7 +3473,88 @@ __global__ __launch_bounds__(1024) void k_part_order(const uint64_t* __restrict_
     if (threadIdx.x == 0) order[nb] = nbig;  // the oversized buckets: order[0, nbig)
 }
 
+// Key-range passes: everything the staging, the split and the partition of a pass take from its
+// level-1 histogram, for every pass of an emission group at once.  One workgroup per pass, launched
+// behind k_pass_hist on the emission's stream, so none of it waits on the main stream before the
+// pass (the five scan kernels and k_part_order did, each behind the previous pass's tail grids).
+// With one histogram row the column sums and offsets of the one-pass path are the row itself:
+//   bstart[NB + 1]  absolute bucket starts (the owners' ranges in order) and the pass's element count
+//   cur1 / cur0     the split's and the staging's cursors (k_stage_init), slice_base the split's slices
+//   order[NB + 1]   k_part_order's list and its nbig (one rank only: after an exchange the partition
+//                   orders the received layout)
+// Copy c of every output is blockIdx.x of set `set0` (PS_CUR0 / PS_SLICES words of cur0 / slice_base
+// per copy): a pass owns its copy, the staging's atomics consume the cursors.
+constexpr uint32_t PS_CUR0 = (1u << SC_L0_BITS) * CUR_STRIDE, PS_SLICES = 80;
+
+__global__ __launch_bounds__(1024) void k_pass_starts(const uint32_t* __restrict__ histg, uint32_t NB, int l0_shift,
+                                                      uint32_t set0, uint64_t* __restrict__ bstart,
+                                                      unsigned long long* __restrict__ cur0,
+                                                      unsigned long long* __restrict__ cur1,
+                                                      uint32_t* __restrict__ slice_base, uint32_t* __restrict__ order) {
+    __shared__ uint32_t s_wave[48];
+    __shared__ uint32_t s_n[(1 << SC_L0_BITS) + 1];
+    const uint32_t c = set0 + blockIdx.x;
+    const uint32_t* hist = histg + (uint64_t)blockIdx.x * NB;
+    bstart += (uint64_t)c * (NB + 1);
+    cur0 += (uint64_t)c * PS_CUR0;
+    cur1 += (uint64_t)c * NB * CUR_STRIDE;
+    slice_base += (uint64_t)c * PS_SLICES;
+    const uint32_t per = (NB + blockDim.x - 1) / blockDim.x;
+    const uint32_t b0 = min(NB, threadIdx.x * per), b1 = min(NB, b0 + per);
+    uint32_t loc = 0;
+    for (uint32_t b = b0; b < b1; ++b) loc += hist[b];
+    uint32_t total;  // a pass of one shard holds fewer than 2^32 elements (size_passes / route_plan check pass_max)
+    uint32_t run = wg_exclusive_scan(loc, s_wave, total);
+    for (uint32_t b = b0; b < b1; ++b) {
+        bstart[b] = run;
+        cur1[(uint64_t)b * CUR_STRIDE] = run;
+        run += hist[b];
+    }
+    if (threadIdx.x == 0) bstart[NB] = total;
+    __syncthreads();
+    const uint32_t n0 = 1u << SC_L0_BITS;
+    if (threadIdx.x < n0) {
+        const uint64_t a = bstart[(uint64_t)threadIdx.x << l0_shift];
+        const uint64_t e = bstart[(uint64_t)(threadIdx.x + 1) << l0_shift];
+        cur0[threadIdx.x * CUR_STRIDE] = a;
+        s_n[threadIdx.x] = (uint32_t)((e - a + SC_SLICE - 1) / SC_SLICE);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t acc = 0;
+        for (uint32_t b = 0; b < n0; ++b) {
+            slice_base[b] = acc;
+            acc += s_n[b];
+        }
+        slice_base[n0] = acc;
+    }
+    if (!order) return;
+    order += (uint64_t)c * (NB + 1);
+    const uint64_t thr = 2 * ((uint64_t)total / max(NB, 1u));
+    loc = 0;
+    for (uint32_t b = b0; b < b1; ++b) loc += hist[b] > thr ? 1u : 0u;
+    uint32_t nbig;
+    uint32_t pos = wg_exclusive_scan(loc, s_wave, nbig);
+    uint32_t sp = b0 - pos;  // the small buckets before b0
+    for (uint32_t b = b0; b < b1; ++b) {
+        if (hist[b] > thr)
+            order[pos++] = b;
+        else
+            order[nbig + sp++] = b;
+    }
+    if (threadIdx.x == 0) order[NB] = nbig;
+}
+
 constexpr uint32_t PT_ROUND = 2048, PT_THREADS = BP_THREADS;
+
+// out of line: the partition's own code stays as it was
+__device__ __noinline__ void copy_small_bucket(const uint64_t* __restrict__ hi, const uint64_t* __restrict__ lo,
+                                               uint64_t* __restrict__ out_hi, uint64_t* __restrict__ out_lo, uint32_t n) {
+    for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) {
+        out_hi[j] = hi[j];
+        out_lo[j] = lo[j];
+    }
+}
 
 __global__ __launch_bounds__(PT_THREADS, 3) void k_partition(BucketArgs A) {
     __shared__ uint32_t s_cur[(1 << MAX_B2) + 1];   // counts, then running write offsets
@@ -3446,8 +3568,12 @@ __global__ __launch_bounds__(PT_THREADS, 3) void k_partition(BucketArgs A) {
     const uint64_t r0 = A.bstart[bucket], r1 = A.bstart[bucket + 1];
     const uint64_t n = r1 - r0;
     uint32_t* tab = A.sub_tab + (uint64_t)bucket * SUB_TAB;
-    if (n == 0 || (n <= (uint64_t)CAP && A.nsrc == 1)) {  // processed in place by k_bucket_process
+    if (n == 0 || (n <= (uint64_t)CAP && A.nsrc == 1)) {
+        // one batch of k_bucket_process, unpartitioned: copied to tmp as it is, so that the group-by
+        // and the pass's tail (big groups, chain lengths) read tmp alone and the next pass's split
+        // may overwrite recs while the tail still runs
         if (threadIdx.x == 0) tab[0] = 0;
+        copy_small_bucket(A.recs_hi + r0, A.recs_lo + r0, A.tmp_hi + r0, A.tmp_lo + r0, (uint32_t)n);
         return;
     }
     const uint64_t rem_mask = (1ull << A.rem_bits) - 1;
@@ -4860,6 +4986,8 @@ __global__ void k_pass_account(const unsigned long long* __restrict__ ctr, unsig
     run[RUN_ACC_BIG_KEPT] += ctr[6];
     run[RUN_ACC_LIGHT_SUB] += ctr[21];
     run[RUN_ACC_LIGHT_ELEMS] += ctr[22];
+    run[RUN_ACC_BPK_TASKS] += ctr[CTR_BPK_TASKS];
+    run[RUN_ACC_BPK_BATCHES] += ctr[CTR_BPK_BATCHES];
     run[RUN_LAST_JOBS] = j;
     if (ctr[3] > jobs_cap || ctr[8 + 3] > jobs2_cap || ctr[5] > big_cap || ctr[8 + 4] > lens_cap)
         atomicOr(&run[RUN_FLAGS], RUN_F_CAP);
@@ -5118,7 +5246,7 @@ struct skm_build {
     hipEvent_t* ev_o = nullptr;
     hipEvent_t* ev_o3 = nullptr;
     float last_ms[15] = {};
-    uint64_t ovf_elems = 0, ovf_kept = 0, ovf_light_sub = 0, ovf_light_elems = 0;
+    uint64_t ovf_elems = 0, ovf_kept = 0, ovf_light_sub = 0, ovf_light_elems = 0, bpk_tasks = 0, bpk_batches = 0;
 
     // host staging (reference emission order, only sequences with a kept function)
     // residues stream to HBM as batches arrive: packed (one 0 separator after each sequence) into
@@ -5168,6 +5296,7 @@ struct skm_build {
     DevBuf d_jobs, d_lens, d_stamps, d_big_desc, d_big_out;
     uint64_t big_cap = 0, n_big = 0, big_kept = 0;
     bool stamps = false;
+    uint32_t n_cus = 0;                 // the device's CUs (k_bucket_process's persistent grid: two workgroups each)
     uint64_t jobs_cap = 0, lens_cap = 0, n_jobs = 0, n_lens = 0;
     uint32_t n_overflow = 0, n_overflow_last = 0;
     uint32_t nwg = 0;
@@ -5679,6 +5808,11 @@ void stage_flush(skm_build* b) {
 
 void prepare_local(skm_build* b) {
     SKM_HIP(hipSetDevice(b->device));
+    if (!b->n_cus) {
+        hipDeviceProp_t prop;
+        SKM_HIP(hipGetDeviceProperties(&prop, b->device));
+        b->n_cus = (uint32_t)std::max(1, prop.multiProcessorCount);
+    }
     set_geometry(b);
     stage_flush(b);  // the last staging buffer; the residues are then resident
     const uint64_t rp = b->rp_total;
@@ -5704,11 +5838,7 @@ void prepare_local(skm_build* b) {
     uint64_t nwg = std::max<uint64_t>(1, std::min<uint64_t>(EX_MAX_WG, ceil_div(rp ? rp : 1, step)));
     b->span = ceil_div(ceil_div(rp ? rp : 1, nwg), step) * step;
     b->nwg = (uint32_t)ceil_div(rp ? rp : 1, b->span);
-    const uint32_t nrb = (uint32_t)ceil_div(b->nwg, SCAN_ROWS);
-    b->d_hist.ensure(sizeof(uint32_t) * (uint64_t)b->nwg * NB);
-    b->d_offs.ensure(sizeof(uint32_t) * (uint64_t)b->nwg * NB);
-    b->d_partial.ensure(sizeof(uint32_t) * (uint64_t)nrb * NB);
-    b->d_rbbase.ensure(sizeof(uint32_t) * (uint64_t)nrb * NB);
+    // (the histogram matrix and its scan buffers: size_local, on the one-pass path only)
     b->d_bstart32.ensure(sizeof(uint32_t) * (NB + 1));
     b->d_bstart.ensure(sizeof(uint64_t) * (NB + 1));
     b->d_owner_start.ensure(sizeof(uint64_t) * 80);
@@ -5823,6 +5953,23 @@ void ensure_local(skm_build* b, uint64_t n) {
     b->cap_local = c;
 }
 
+// The copy of d_bstart / d_cur0 / d_cur1 / d_slices / d_part_order that a pass owns.  With key-range
+// passes k_pass_starts fills one copy per pass of an emission group, in two sets that alternate by
+// group parity: the next group is emitted while this group's last pass still reads its own.  The
+// one-pass path has the one copy its scan kernels write.
+inline uint32_t pass_copies(const skm_build* b) { return b->pass_bits ? 2u * b->emit_g : 1u; }
+inline uint32_t pass_copy(const skm_build* b, uint32_t pass) {
+    return b->pass_bits ? ((pass / b->emit_g) & 1u) * b->emit_g + pass % b->emit_g : 0u;
+}
+void ensure_pass_copies(skm_build* b) {
+    const uint64_t NB = 1ull << (b->owner_bits + b->b1_bits), nc = pass_copies(b);
+    b->d_bstart.ensure(sizeof(uint64_t) * (NB + 1) * nc);
+    b->d_cur0.ensure(8ull * PS_CUR0 * nc);
+    b->d_cur1.ensure(8ull * NB * CUR_STRIDE * nc);
+    b->d_slices.ensure(4ull * PS_SLICES * nc);
+    b->d_part_order.ensure(4ull * (NB + 1) * nc);
+}
+
 // extract buffers (one pass of this shard), the pass-id bytes, and with passes the kept arena
 void size_local(skm_build* b) {
     const uint64_t W = std::max<uint64_t>(b->pass_max, 1);
@@ -5852,12 +5999,17 @@ void size_local(skm_build* b) {
         uint32_t nwg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(stage_wg, ceil_div(W, (uint64_t)SC_ROUND * 4)));
         b->pf_span = ceil_div(ceil_div(W, nwg), (uint64_t)SC_ROUND) * SC_ROUND;
         b->pf_nwg = (uint32_t)std::max<uint64_t>(1, ceil_div(W, b->pf_span));
-        // the histogram matrix of a pass may use every extract workgroup row
-        b->d_hist.ensure(sizeof(uint32_t) * (uint64_t)EX_MAX_WG * NB);
-        b->d_offs.ensure(sizeof(uint32_t) * (uint64_t)EX_MAX_WG * NB);
-        b->d_partial.ensure(sizeof(uint32_t) * (uint64_t)ceil_div(EX_MAX_WG, SCAN_ROWS) * NB);
-        b->d_rbbase.ensure(sizeof(uint32_t) * (uint64_t)ceil_div(EX_MAX_WG, SCAN_ROWS) * NB);
+    } else {
+        // one pass: the [workgroup][bucket] histogram matrix and its scan buffers (k_extract, k_colsum,
+        // k_bstart, k_coloffs); with key-range passes k_pass_starts works from the pass's one row
+        const uint64_t NB = 1ull << (b->owner_bits + b->b1_bits);
+        const uint64_t nrb = ceil_div(b->nwg, SCAN_ROWS);
+        b->d_hist.ensure(sizeof(uint32_t) * (uint64_t)b->nwg * NB);
+        b->d_offs.ensure(sizeof(uint32_t) * (uint64_t)b->nwg * NB);
+        b->d_partial.ensure(sizeof(uint32_t) * nrb * NB);
+        b->d_rbbase.ensure(sizeof(uint32_t) * nrb * NB);
     }
+    ensure_pass_copies(b);
 }
 
 void size_arena(skm_build* b) {
@@ -6188,6 +6340,12 @@ void emit_group(skm_build* b, uint32_t g, hipStream_t st) {
     SKM_HIP(hipMemsetAsync(b->d_histg.p, 0, sizeof(uint32_t) * NB * G, st));
     SKM_LAUNCH(b, k_pass_hist, dim3(256, G), dim3(PH_THREADS), 4u * NB, st, b->d_posg.as<uint64_t>(), cap,
                b->d_npos.as<unsigned long long>() + (uint64_t)g * G, NB, rem_bits, b->d_histg.as<uint32_t>());
+    // every pass's bucket starts, cursors, slices and partition order from its histogram row, into
+    // the pass's copies of this group's set
+    SKM_LAUNCH(b, k_pass_starts, dim3(G), dim3(1024), 0, st, b->d_histg.as<uint32_t>(), NB,
+               b->owner_bits + b->b1_bits - SC_L0_BITS, (g & 1u) * G, b->d_bstart.as<uint64_t>(),
+               b->d_cur0.as<unsigned long long>(), b->d_cur1.as<unsigned long long>(), b->d_slices.as<uint32_t>(),
+               b->world == 1 && b->tune.part_order ? b->d_part_order.as<uint32_t>() : nullptr);
     SKM_HIP(hipGetLastError());
     if (st != b->stream) SKM_HIP(hipEventRecord(b->ev_emit, st));
 }
@@ -6196,8 +6354,8 @@ void emit_group(skm_build* b, uint32_t g, hipStream_t st) {
 inline unsigned long long* pass_ctr(skm_build* b) { return b->d_ctr.as<unsigned long long>() + 32; }
 
 // the main stream waits for the previous pass's tail (tail_async) before it overwrites what the tail
-// reads (the split's recs, then the partition's tmp, the counters, the job lists) or reads what it
-// writes (the stash cursors, the kept arena's totals)
+// reads (the partition's tmp, the counters, the job lists; not recs: k_partition is its last reader)
+// or reads what it writes (the stash cursors, the kept arena's totals)
 void join_tail(skm_build* b) {
     if (!b->tail_pending) return;
     SKM_HIP(hipStreamWaitEvent(b->stream, b->ev_tail_done, 0));
@@ -6252,25 +6410,31 @@ void phase_extract(skm_build* b, uint32_t pass) {
     }
     SKM_HIP(hipGetLastError());
     SKM_HIP(hipEventRecord(b->ev[1], st));
-    // ---- 2. scan ----
-    const uint32_t nrb = (uint32_t)ceil_div(hist_rows, SCAN_ROWS);
-    dim3 gsc((NB + 255) / 256, nrb);
-    SKM_LAUNCH(b, k_colsum, gsc, dim3(256), 0, st, X.hist, hist_rows, NB, b->d_partial.as<uint32_t>());
-    SKM_LAUNCH(b, k_bstart, dim3(1), dim3(1024), 0, st, b->d_partial.as<uint32_t>(), nrb, NB, b->b1_bits,
-                       b->d_rbbase.as<uint32_t>(), b->d_bstart32.as<uint32_t>(), b->d_owner_start.as<uint64_t>(), nowners);
-    SKM_LAUNCH(b, k_coloffs, gsc, dim3(256), 0, st, X.hist, b->d_rbbase.as<uint32_t>(), hist_rows,
-                       NB, b->d_offs.as<uint32_t>());
-    SKM_LAUNCH(b, k_abs_starts, dim3((NB + 1 + 255) / 256), dim3(256), 0, st, b->d_bstart32.as<uint32_t>(),
-                       b->d_owner_start.as<uint64_t>(), NB, b->b1_bits, nowners, b->d_bstart.as<uint64_t>());
-    SKM_HIP(hipGetLastError());
+    // ---- 2. scan (one pass; with key-range passes the pass's copies come from k_pass_starts, at
+    //      emission time, and nothing is launched here) ----
+    const uint32_t pc = pass_copy(b, pass);
+    uint64_t* bstart = b->d_bstart.as<uint64_t>() + (uint64_t)pc * (NB + 1);
+    unsigned long long* cur0 = b->d_cur0.as<unsigned long long>() + (uint64_t)pc * PS_CUR0;
+    unsigned long long* cur1 = b->d_cur1.as<unsigned long long>() + (uint64_t)pc * NB * CUR_STRIDE;
+    uint32_t* slices = b->d_slices.as<uint32_t>() + (uint64_t)pc * PS_SLICES;
+    if (!b->pass_bits) {
+        const uint32_t nrb = (uint32_t)ceil_div(hist_rows, SCAN_ROWS);
+        dim3 gsc((NB + 255) / 256, nrb);
+        SKM_LAUNCH(b, k_colsum, gsc, dim3(256), 0, st, X.hist, hist_rows, NB, b->d_partial.as<uint32_t>());
+        SKM_LAUNCH(b, k_bstart, dim3(1), dim3(1024), 0, st, b->d_partial.as<uint32_t>(), nrb, NB, b->b1_bits,
+                           b->d_rbbase.as<uint32_t>(), b->d_bstart32.as<uint32_t>(), b->d_owner_start.as<uint64_t>(), nowners);
+        SKM_LAUNCH(b, k_coloffs, gsc, dim3(256), 0, st, X.hist, b->d_rbbase.as<uint32_t>(), hist_rows,
+                           NB, b->d_offs.as<uint32_t>());
+        SKM_LAUNCH(b, k_abs_starts, dim3((NB + 1 + 255) / 256), dim3(256), 0, st, b->d_bstart32.as<uint32_t>(),
+                           b->d_owner_start.as<uint64_t>(), NB, b->b1_bits, nowners, bstart);
+        SKM_HIP(hipGetLastError());
+    }
     SKM_HIP(hipEventRecord(b->ev[2], st));
     // ---- 3. scatter: 64-way staged pass into tmp, then the split into the final buckets ----
-    const int l0_shift = nbits - SC_L0_BITS;
-    b->d_cur0.ensure(8ull * 64 * CUR_STRIDE);
-    b->d_cur1.ensure(8ull * NB * CUR_STRIDE);
-    b->d_slices.ensure(4 * 80);
-    SKM_LAUNCH(b, k_stage_init, dim3((NB + 255) / 256), dim3(256), 0, st, b->d_bstart.as<uint64_t>(), NB, l0_shift,
-                       b->d_cur0.as<unsigned long long>(), b->d_cur1.as<unsigned long long>(), b->d_slices.as<uint32_t>());
+    if (!b->pass_bits) {
+        SKM_LAUNCH(b, k_stage_init, dim3((NB + 255) / 256), dim3(256), 0, st, bstart, NB, nbits - SC_L0_BITS, cur0, cur1,
+                   slices);
+    }
     // the level-0 staging: tmp, or (tail_async) a buffer of its own, so it overlaps the previous
     // pass's tail, which still reads tmp and recs
     const bool sep = tail_async_on(b);
@@ -6282,21 +6446,20 @@ void phase_extract(skm_build* b, uint32_t pass) {
                    b->d_posg.as<uint64_t>() + (uint64_t)(pass % b->emit_g) * std::max<uint64_t>(b->pass_max, 1),
                    b->d_npos.as<unsigned long long>() + pass,
                    b->d_seloff.as<uint64_t>() + (uint64_t)pass * (b->sel_wg + 1), b->sel_wg, b->sel_span,
-                   b->d_cur0.as<unsigned long long>(), stg_hi, stg_lo);
+                   cur0, stg_hi, stg_lo);
     else if (b->pass_bits)
         SKM_LAUNCH_AS(b, "k_extract_stage_pos", (k_extract_stage_pos<SC_ROUND, 2>), dim3(nwg), dim3(EX_THREADS), 0, st, X,
                    b->d_posg.as<uint64_t>() + (uint64_t)(pass % b->emit_g) * std::max<uint64_t>(b->pass_max, 1),
                    b->d_npos.as<unsigned long long>() + pass,
                    b->d_seloff.as<uint64_t>() + (uint64_t)pass * (b->sel_wg + 1), b->sel_wg, b->sel_span,
-                   b->d_cur0.as<unsigned long long>(), stg_hi, stg_lo);
+                   cur0, stg_hi, stg_lo);
     else
-        SKM_LAUNCH(b, k_extract_stage, dim3(nwg), dim3(EX_THREADS), 0, st, X, b->d_cur0.as<unsigned long long>(),
-                           stg_hi, stg_lo);
-    join_tail(b);  // the split overwrites the element buffer the previous pass's tail reads
+        SKM_LAUNCH(b, k_extract_stage, dim3(nwg), dim3(EX_THREADS), 0, st, X, cur0, stg_hi, stg_lo);
+    // (the split overwrites recs, which only k_partition reads: the previous pass's tail reads tmp and
+    // is joined before the partition, in phase_group)
     const uint32_t nsl = (uint32_t)(ceil_div(b->pass_max, SC_SLICE) + (1u << SC_L0_BITS));
     SKM_LAUNCH(b, k_split_stage, dim3(nsl), dim3(EX_THREADS), 0, st, stg_hi,
-                       stg_lo, b->d_bstart.as<uint64_t>(), nbits, b->d_slices.as<uint32_t>(),
-                       b->d_cur1.as<unsigned long long>(), b->d_recs_hi.as<uint64_t>(), b->d_recs_lo.as<uint64_t>());
+                       stg_lo, bstart, nbits, slices, cur1, b->d_recs_hi.as<uint64_t>(), b->d_recs_lo.as<uint64_t>());
     SKM_HIP(hipGetLastError());
     SKM_HIP(hipEventRecord(b->ev[3], st));
 }
@@ -6314,7 +6477,8 @@ void exchange(const Ranks& bs, uint32_t pass) {
     for (auto* b : bs) {
         b->d_cnt_send.ensure(4ull * NB);
         b->d_cnt_recv.ensure(4ull * NB);
-        SKM_LAUNCH(b, k_send_counts, dim3((NB + 255) / 256), dim3(256), 0, b->stream, b->d_bstart.as<uint64_t>(), NB, NB1,
+        SKM_LAUNCH(b, k_send_counts, dim3((NB + 255) / 256), dim3(256), 0, b->stream,
+                   b->d_bstart.as<uint64_t>() + (uint64_t)pass_copy(b, pass) * ((1ull << (b->owner_bits + b->b1_bits)) + 1), NB, NB1,
                    (uint32_t)W, b->d_xs.as<unsigned long long>() + (uint64_t)pass * W, b->d_run.as<unsigned long long>(),
                    b->d_cnt_send.as<uint32_t>());
         cx.send.push_back(b->d_cnt_send.as<uint8_t>());
@@ -6500,8 +6664,8 @@ void phase_group(skm_build* b, uint32_t pass) {
     hipStream_t st = b->stream, st2 = b->stream2, st3 = b->stream3;
     const bool multi = b->world > 1;
     const uint32_t NB1 = 1u << b->b1_bits;
-    // if the previous pass's tail is still pending (the split joins it, so today it never is), it
-    // still reads tmp, the counters and the job lists, all written from here on
+    // the previous pass's tail still reads tmp, the counters and the job lists, all written from
+    // here on; the staging and the split before this point ran beside it
     join_tail(b);
     SKM_HIP(hipEventRecord(b->ev[4], st));
     // per-pass counters; [0] (kept k-mers: the arena cursor) and the signature flags run over
@@ -6516,7 +6680,8 @@ void phase_group(skm_build* b, uint32_t pass) {
     A.recs_lo = (multi ? b->d_rlo : b->d_recs_lo).as<uint64_t>();
     A.tmp_hi = b->d_tmp_hi.as<uint64_t>();
     A.tmp_lo = b->d_tmp_lo.as<uint64_t>();
-    A.bstart = multi ? b->d_vstart.as<uint64_t>() : b->d_bstart.as<uint64_t>();
+    const uint32_t pc = pass_copy(b, pass);  // world 1: NB1 buckets in the pass's copies
+    A.bstart = multi ? b->d_vstart.as<uint64_t>() : b->d_bstart.as<uint64_t>() + (uint64_t)pc * (NB1 + 1);
     A.seg_start = multi ? b->d_seg_start.as<uint64_t>() : nullptr;
     A.seg_len = multi ? b->d_seg_len.as<uint32_t>() : nullptr;
     A.nsrc = multi ? (uint32_t)b->world : 1u;
@@ -6549,9 +6714,10 @@ void phase_group(skm_build* b, uint32_t pass) {
     // ---- 4a. level-2 partition (the oversized buckets' workgroups first) ----
     A.order = nullptr;
     if (b->tune.part_order) {
-        b->d_part_order.ensure(4ull * (NB1 + 1));
-        SKM_LAUNCH(b, k_part_order, dim3(1), dim3(1024), 0, st, A.bstart, NB1, b->d_part_order.as<uint32_t>());
-        A.order = b->d_part_order.as<uint32_t>();
+        // key-range passes on one rank: k_pass_starts wrote the pass's list at emission time; after an
+        // exchange the order is that of the received layout (copy 0 is then free: no rank writes it)
+        A.order = b->d_part_order.as<uint32_t>() + (multi ? 0 : (uint64_t)pc * (NB1 + 1));
+        if (multi || !b->pass_bits) SKM_LAUNCH(b, k_part_order, dim3(1), dim3(1024), 0, st, A.bstart, NB1, b->d_part_order.as<uint32_t>());
     }
     SKM_LAUNCH(b, k_partition, dim3(NB1), dim3(BP_THREADS), 0, st, A);
     SKM_HIP(hipGetLastError());
@@ -6565,7 +6731,7 @@ void phase_group(skm_build* b, uint32_t pass) {
     if (multi) {  // the received element count: k_recv_plan's vstart[NB1]
         nloc_d = reinterpret_cast<const unsigned long long*>(b->d_vstart.as<uint64_t>() + NB1);
     } else {
-        nloc_d = reinterpret_cast<const unsigned long long*>(b->d_bstart.as<uint64_t>() + NB1);
+        nloc_d = reinterpret_cast<const unsigned long long*>(A.bstart + NB1);
     }
     const uint32_t split_min = (uint32_t)std::max(b->tune.split_min, CAP + 1);
     const uint32_t key_min = (uint32_t)std::max(b->tune.heavy_min, 2);
@@ -6696,7 +6862,8 @@ void phase_group(skm_build* b, uint32_t pass) {
     BA.flags = A.flags;
     BA.out = b->d_big_out.as<BigOut>();
     SKM_HIP(hipEventRecord(b->ev[11], st));
-    SKM_LAUNCH(b, k_bucket_process, dim3(NB1), dim3(BPK_THREADS), 0, st, A);
+    // persistent: two workgroups per CU take the pass's (bucket, part) tasks from ctr_d[CTR_BPK_TASK]
+    SKM_LAUNCH(b, k_bucket_process, dim3(std::min<uint32_t>(NB1 * BPK_PARTS, 2u * b->n_cus)), dim3(BPK_THREADS), 0, st, A);
     SKM_HIP(hipGetLastError());
     SKM_HIP(hipEventRecord(b->ev[5], st));
     if (b->tune.serial_overflow) launch_overflow();
@@ -6708,7 +6875,7 @@ void phase_group(skm_build* b, uint32_t pass) {
         b->emit_q = (pass + 1) / b->emit_g;
     }
     // the pass's tail: on the main stream, or (tail_async) on its own stream beside the next pass's
-    // staging -- the next split waits for it (join_tail)
+    // staging and split -- the next partition waits for it (join_tail)
     const bool tail_async = tail_async_on(b);
     hipStream_t tt = tail_async ? b->stream_tail : st;
     if (tail_async) {
@@ -7035,6 +7202,8 @@ void phase_final(skm_build* b) {
     b->big_kept = R[RUN_ACC_BIG_KEPT];
     b->ovf_light_sub = R[RUN_ACC_LIGHT_SUB];
     b->ovf_light_elems = R[RUN_ACC_LIGHT_ELEMS];
+    b->bpk_tasks = R[RUN_ACC_BPK_TASKS];
+    b->bpk_batches = R[RUN_ACC_BPK_BATCHES];
     b->n_local = R[RUN_ACC_GROUPED];
     b->ran = true;
 }
@@ -7694,7 +7863,7 @@ int skm_debug_div_check(uint64_t nm, uint32_t per, uint64_t* mismatches) {
 int skm_build_counters(skm_build* b, uint64_t* out, int cap) {
     if (!b || !out) return SKM_E_ARG;
     auto us = [](double sec) { return (uint64_t)(sec * 1e6); };
-    const uint64_t v[48] = {b->n_windows, b->n_kept, b->n_overflow, b->n_jobs, b->n_lens, b->nseq, b->n_local,
+    const uint64_t v[50] = {b->n_windows, b->n_kept, b->n_overflow, b->n_jobs, b->n_lens, b->nseq, b->n_local,
                             b->ovf_elems, b->ovf_kept, b->n_big, b->big_kept, 1ull << b->pass_bits, b->valid_total,
                             b->giant_jobs, b->giant_max, b->n_redo, b->tot_cap, b->split_cap, b->long_cap,
                             b->long_jobs_cap, b->demand[0], b->demand[1], b->demand[2], b->demand[3],
@@ -7705,8 +7874,9 @@ int skm_build_counters(skm_build* b, uint64_t* out, int cap) {
                             (uint64_t)(1e3 * b->handoff.sort_ms), (uint64_t)(1e3 * b->handoff.gather_ms),
                             (uint64_t)(1e3 * b->handoff.d2h_ms), b->handoff.max_chunk,
                             (uint64_t)b->handoff.wide_index, b->kept_cap, b->free_after_prepare,
-                            0ull /* [45] reserved */, b->ovf_light_sub, b->ovf_light_elems};
-    int n = std::min(cap, 48);
+                            0ull /* [45] reserved */, b->ovf_light_sub, b->ovf_light_elems, b->bpk_tasks,
+                            b->bpk_batches};
+    int n = std::min(cap, 50);
     for (int i = 0; i < n; ++i) out[i] = v[i];
     return n;
 }
