@@ -416,6 +416,45 @@ int skm_mph_build_device_ex(const uint64_t* keys, const skm_stored_kmer_data* da
                             const char* mph_path, const char* dat_path, int device, int verify,
                             skm_mph_stats* stats);
 
+/* The BDZ signature DB -- what build_perfect_hash writes (perfect_hash.h:11-69) and
+ * CmphKmerDb::load_hash / load_data read back (cmph_kmer.h:95-104) -- made and opened on the
+ * device from a finished build, without the host copy of the kept set, the second upload and the
+ * file round trip of skm_build_finish + skm_mph_build_device + skm_db_open. */
+typedef struct skm_mph_db_opts {
+    uint32_t seed;          /* as skm_mph_build_device's seed                                   */
+    int32_t  release_work;  /* as skm_kept_db_opts.release_work, the same contract              */
+    int32_t  verify;        /* as skm_mph_build_device_ex's verify                              */
+    int32_t  pad;
+    const char* mph_path;   /* NULL = not written                                               */
+    const char* dat_path;   /* NULL = not written                                               */
+} skm_mph_db_opts;
+
+/* A full BDZ DB over the kept k-mers of b's last run, on b's device, independent of b: every call
+ * that takes a DB opened by skm_db_open works on it (skm_db_lookup, _lookup_fm, skm_annotate,
+ * skm_query_*, skm_matrix_*, skm_matrix_batch_*), and skm_db_table_info returns zeros as for any
+ * BDZ DB.  opts NULL = seed 1, nothing released, checked or written.  Runs the build first if it
+ * has not run since prepare.  world_size > 1 returns SKM_E_STATE; more kept k-mers than one BDZ
+ * holds (n = 3r < 2^32, about 3.4 G keys) SKM_E_ARG; a failed device allocation SKM_E_OOM with the
+ * bytes asked for and the bytes free in skm_last_error(), and b stays usable.  release_work = 1
+ * is skm_build_kept_db's: the same buffers go, before anything is allocated, and the same calls
+ * return SKM_E_STATE afterwards.
+ * From 1024 kept k-mers on, everything stays on the device: the peel, assign and place kernels of
+ * skm_mph_build_device read the keys and records in place from the arena (its keys are distinct by
+ * construction, so there is no duplicate check), the rank table is counted and scanned on the
+ * device from g, and the records, record words and b = 7 pair lines are written straight into the
+ * DB's buffers.  The peel does not depend on the order of the keys, so the image and the .dat are
+ * byte for byte those of skm_mph_build_device over the sorted kept set with the same seed.  g and
+ * the rank table come to the host only when mph_path is given (the cmph dump); dat_path is written
+ * from the DB's record array.  Below 1024 kept k-mers the sorted kept set is downloaded and the
+ * host builder runs, as in skm_mph_build_device.  stats (may be NULL): upload_s stays 0, write_s
+ * covers the files. */
+int skm_build_mph_db(skm_build* b, const skm_mph_db_opts* opts, skm_db** out, skm_mph_stats* stats);
+/* host only: for n kept k-mers, out[0] = r of the first attempt (ceil(1.23 n / 3) made odd),
+ * [1] = vertices (3r), [2] = device bytes of the open DB, [3] = the most device bytes live at one
+ * time during skm_build_mph_db, the arena not counted (the peel state: 16 bytes per vertex and 5
+ * per key).  n above the BDZ limit returns SKM_E_ARG.  Callers decide on release_work with it. */
+int skm_mph_db_plan(uint64_t n, uint64_t out[4]);
+
 /* ------------------------------------------------------------------------------------------
  * Function calling.  Replaces FunctionCaller<CmphKmerDb>::process_aa_seq for a batch of query
  * sequences (call_functions.tcc:259-338 + HitSet :6-108, window iterator kmer_data.h:76-102).

@@ -82,6 +82,11 @@ class _KeptDbOpts(C.Structure):
     _fields_ = [("load_pct", C.c_uint32), ("release_work", C.c_int32), ("slots", C.c_uint64)]
 
 
+class _MphDbOpts(C.Structure):
+    _fields_ = [("seed", C.c_uint32), ("release_work", C.c_int32), ("verify", C.c_int32), ("pad", C.c_int32),
+                ("mph_path", C.c_char_p), ("dat_path", C.c_char_p)]
+
+
 class _Pairs(C.Structure):
     _fields_ = [("pairs", C.POINTER(C.c_uint32)), ("n", C.c_uint64), ("n_hits", C.c_uint64)]
 
@@ -126,6 +131,8 @@ _SIGS = {
     "skm_build_kept_db": (C.c_int, [_P, C.POINTER(_KeptDbOpts), C.POINTER(_P)]),
     "skm_kept_db_plan": (C.c_int, [C.c_uint64, C.POINTER(_KeptDbOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "skm_debug_kept_slot": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "skm_build_mph_db": (C.c_int, [_P, C.POINTER(_MphDbOpts), C.POINTER(_P), C.c_void_p]),
+    "skm_mph_db_plan": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
     "skm_db_lookup_fm": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "skm_db_table_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     "skm_db_size": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
@@ -426,6 +433,23 @@ class SignatureBuilder:
         _check(lib().skm_build_kept_db(self._h, C.byref(opts), C.byref(h)))
         return DeviceKeptKmerDb(h, self.device)
 
+    def mph_db(self, seed: int = 1, release_work: bool = False, verify: bool = False, mph_path: str | None = None,
+               dat_path: str | None = None) -> "CmphKmerDb":
+        """skm_build_mph_db: the BDZ signature DB (build_perfect_hash + CmphKmerDb, perfect_hash.h:11-69,
+        cmph_kmer.h:95-104) over the kept k-mers of the last run, built and opened on the device from
+        the resident arena -- no host copy of the kept set and no file round trip.  The image and the
+        .dat, written only where a path is given, are those of mph_build(sorted kept set, seed,
+        device=...).  release_work as in kept_db.  The returned DB is independent of the builder; its
+        `stats` are mph_build_device's dict (upload_s stays 0)."""
+        opts = _MphDbOpts(int(seed), 1 if release_work else 0, 1 if verify else 0, 0,
+                          mph_path.encode() if mph_path else None, dat_path.encode() if dat_path else None)
+        h = C.c_void_p()
+        st = _MphStats()
+        _check(lib().skm_build_mph_db(self._h, C.byref(opts), C.byref(h), C.byref(st)))
+        db = CmphKmerDb(device=self.device, handle=h)
+        db.stats = {n: getattr(st, n) for n, _ in _MphStats._fields_ if n != "pad"}
+        return db
+
     @staticmethod
     def _kept(k) -> KeptKmers:
         """The library's arrays without a copy: keys / data view the hand-off's host arrays, which
@@ -601,10 +625,12 @@ class CmphKmerDb:
     KmerSize = K
 
     def __init__(self, file_base: str | None = None, device: int = 0, mph: bytes | None = None,
-                 dat: bytes | None = None):
+                 dat: bytes | None = None, handle=None):
         self._h = C.c_void_p()
         self.device = device
-        if file_base is not None:
+        if handle is not None:  # an open skm_db (SignatureBuilder.mph_db); this object owns it
+            self._h = handle
+        elif file_base is not None:
             _check(lib().skm_db_open(C.byref(self._h), (file_base + ".mph").encode(), (file_base + ".dat").encode(),
                                      device))
         else:
@@ -695,6 +721,15 @@ def kept_db_plan(n: int, load_pct: int = 0, slots: int = 0) -> tuple:
     t, b = C.c_uint64(), C.c_uint64()
     _check(lib().skm_kept_db_plan(int(n), C.byref(opts), C.byref(t), C.byref(b)))
     return t.value, b.value
+
+
+def mph_db_plan(n: int) -> tuple:
+    """skm_mph_db_plan (host only): for n kept k-mers, (r of the first attempt, vertices 3r, device
+    bytes of the open BDZ DB, most device bytes live while SignatureBuilder.mph_db builds it -- the
+    arena not counted)."""
+    v = (C.c_uint64 * 4)()
+    _check(lib().skm_mph_db_plan(int(n), v))
+    return tuple(int(x) for x in v)
 
 
 def kept_slot(key: int, slots: int) -> int:

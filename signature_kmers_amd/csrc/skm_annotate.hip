@@ -33,6 +33,7 @@
 #include "skm_bdz.h"
 #include "skm_common.h"
 #include "skm_lookup.h"
+#include "skm_mphdb.h"
 #include "skm_pool.h"
 #include "skm_select.h"
 #include "skm_util.h"
@@ -1097,8 +1098,13 @@ void db_upload_kept(skm_db* db, const uint64_t* keys, const skm_stored_kmer_data
     }
 }
 
-// hipMalloc of the range-reduced table; a failure names the bytes asked for and the bytes free
-void alloc_kept_table(DevBuf& tab, uint64_t bytes) {
+// hipMalloc of one of the large buffers of a DB made from a build's arena (the range-reduced table,
+// the BDZ construction's state and the BDZ DB's arrays) into an empty or smaller DevBuf; a failure
+// names the bytes asked for and the bytes free
+void alloc_reported(DevBuf& buf, uint64_t bytes, const char* what) {
+    if (buf.p && bytes <= buf.bytes) return;
+    buf.release();
+    bytes = std::max<uint64_t>(bytes, 16);
     void* p = nullptr;
     const hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) {
@@ -1106,11 +1112,11 @@ void alloc_kept_table(DevBuf& tab, uint64_t bytes) {
         size_t fr = 0, tot = 0;
         (void)hipMemGetInfo(&fr, &tot);
         throw Error(e == hipErrorOutOfMemory ? SKM_E_OOM : SKM_E_HIP,
-                    "kept k-mer table: " + std::to_string(bytes) + " bytes asked for, " + std::to_string(fr) +
+                    std::string(what) + ": " + std::to_string(bytes) + " bytes asked for, " + std::to_string(fr) +
                         " bytes free on the device (" + hipGetErrorString(e) + ")");
     }
-    tab.p = p;
-    tab.bytes = bytes;
+    buf.p = p;
+    buf.bytes = bytes;
 }
 
 bool read_file(const char* path, std::vector<uint8_t>& out) {
@@ -1277,7 +1283,7 @@ skm_db* db_from_device_kept(const uint64_t* d_keys, const skm_stored_kmer_data* 
     db->exact = db->ranged = true;
     db->m = (uint32_t)n;
     db->dat_records = 0;  // the slots carry the record word; nothing reads the records (D.dat stays null)
-    alloc_kept_table(db->d_xtab, 16 * slots);
+    alloc_reported(db->d_xtab, 16 * slots, "kept k-mer table");
     DevBdz& D = db->dev;
     D = DevBdz{};
     D.m = (uint32_t)n;
@@ -1742,9 +1748,13 @@ void skm_calls_free(skm_calls* c) {
 //   k_mph_assign    rounds in reverse: the free vertex gets (position - g[u1] - g[u2]) mod 3
 //                   (unassigned = 3 = 0 mod 3); edges of one round never share a free vertex
 //                   and their other vertices were freed in later rounds, so a round is parallel
-//   rank table on the host from g; records placed by the device lookup.
+//   rank table on the host from g (skm_mph_build_device_ex) or on the device (skm_build_mph_db:
+//   k_mph_rank_tiles, k_scan_sums, k_mph_rank_write); records placed by the device lookup.
 // Any acyclic peel order gives a valid minimal perfect hash; this one is deterministic (the
-// frontier ORDER depends on atomics, the peeled SET of a round and the g values do not).
+// frontier ORDER depends on atomics, the peeled SET of a round and the g values do not), and it
+// does not depend on the order of the keys either: an edge id enters only the sums that name a
+// vertex's last edge, and an edge is peeled by its first degree-1 vertex by position.  So
+// skm_build_mph_db, which reads a build's arena in place, gives the image of the sorted keys.
 //
 // Sized for the headline build's kept set (C3: 2.89 G keys, 3.55 G vertices): cmph's BDZ keeps
 // m, n and r as cmph_uint32, so every key, edge and vertex index here is a u32 and the limit is
@@ -1917,8 +1927,10 @@ __global__ void k_mph_assign(const uint32_t* __restrict__ pe, const uint8_t* __r
 
 // bad: 1 = a key's slot >= m, 2 = two keys on one slot (the slot bitmap), 4 = the pair-line
 // search disagrees with the generic one, 8 = a .dat record differs from its key's record
+// fm != nullptr: the record word of the slot as well (k_dat_fm's word, without its pass over dat)
 __global__ void k_mph_place(const uint64_t* __restrict__ keys, uint32_t m, DevBdz D, const uint16_t* __restrict__ data,
-                            uint16_t* __restrict__ dat, uint32_t* __restrict__ bits, uint32_t* __restrict__ bad) {
+                            uint16_t* __restrict__ dat, uint32_t* __restrict__ fm, uint32_t* __restrict__ bits,
+                            uint32_t* __restrict__ bad) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const uint64_t k = keys[i];
@@ -1931,8 +1943,57 @@ __global__ void k_mph_place(const uint64_t* __restrict__ keys, uint32_t m, DevBd
         const uint32_t bit = 1u << (idx & 31u);
         if (atomicOr(&bits[idx >> 5], bit) & bit) atomicOr(bad, 2u);
     }
+    uint16_t rec[5];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) dat[5ull * idx + j] = data[5ull * i + j];
+    for (int j = 0; j < 5; ++j) rec[j] = data[5ull * i + j];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) dat[5ull * idx + j] = rec[j];
+    if (fm) fm[idx] = ((uint32_t)rec[1] << 16) | (uint32_t)rec[2];  // function_index, mean
+}
+
+// ---- the rank table on the device (skm_build_mph_db) ----
+// The assigned vertices of rank block q (128 vertices = eight g words), as the host loop of
+// skm_mph_build_device_ex counts them: entries past n keep the value 3, words at or past gwords
+// count as unassigned.
+__device__ __forceinline__ uint32_t mph_block_assigned(const uint32_t* __restrict__ g, uint64_t gwords, uint64_t q) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        const uint64_t gi = 8 * q + (uint64_t)w;
+        const uint32_t x = gi < gwords ? g[gi] : 0xFFFFFFFFu;
+        c += 16u - unassigned_in(x);
+    }
+    return c;
+}
+// inclusive sum over the wave (lane 63 holds the wave's total)
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)x, d, 64);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
+// A tile is the 64 rank blocks of one wave (8192 vertices), one block per lane.  k_mph_rank_tiles
+// writes every tile's count of assigned vertices; k_scan_sums turns the counts into exclusive
+// offsets (and their total, which must be m); k_mph_rank_write counts again and writes rank[q] =
+// its tile's offset + the assigned vertices of the tile's blocks before q.  Blocks are whole tiles
+// (256 threads = 4 tiles), so every lane of a wave is live in the shuffles.
+constexpr uint32_t MPH_RANK_TILE = 64;
+__global__ __launch_bounds__(256) void k_mph_rank_tiles(const uint32_t* __restrict__ g, uint64_t gwords, uint32_t nrank,
+                                                        uint64_t* __restrict__ tile_sums) {
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;  // nrank <= 2^25: no wrap
+    const uint32_t c = wave_incl_sum(q < nrank ? mph_block_assigned(g, gwords, q) : 0u);
+    if ((threadIdx.x & 63u) == 63u && (q - 63u) < nrank) tile_sums[q / MPH_RANK_TILE] = c;
+}
+__global__ __launch_bounds__(256) void k_mph_rank_write(const uint32_t* __restrict__ g, uint64_t gwords, uint32_t nrank,
+                                                        const uint64_t* __restrict__ tile_offs,
+                                                        uint32_t* __restrict__ rank) {
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t own = q < nrank ? mph_block_assigned(g, gwords, q) : 0u;
+    const uint32_t incl = wave_incl_sum(own);
+    if (q < nrank) rank[q] = (uint32_t)tile_offs[q / MPH_RANK_TILE] + incl - own;
 }
 
 // the b == 7 (g word, rank) pair lines of the annotate lookup (db_upload's layout), built on the
@@ -2017,6 +2078,113 @@ bool write_device_file(const char* path, const void* dev, uint64_t bytes, int de
     for (auto& x : th) x.join();
     return ::close(fd) == 0 && ok.load();
 }
+
+void write_mph_image(const char* path, const Bdz& h) {
+    std::vector<uint8_t> img = bdz_dump(h);
+    std::ofstream fm(path, std::ios::binary);
+    SKM_CHECK((bool)fm, SKM_E_IO, std::string("cannot write ") + path);
+    fm.write((const char*)img.data(), (std::streamsize)img.size());
+    SKM_CHECK((bool)fm, SKM_E_IO, "write failed");
+}
+
+// The peel of skm_mph_build_device_ex and skm_build_mph_db: the peeled edges in peel order (pe,
+// pp), the boundaries of the rounds, and the geometry (h.r, h.n, h.ranktablesize, h.seed; P) of the
+// attempt that peeled every edge.
+struct MphPeel {
+    DevBuf dpe, dpp, dcnt;
+    std::vector<uint32_t> rounds;
+    MphDev P{};
+};
+
+// Peels the 3-hypergraph of the m keys at dkeys (device memory, read in place), drawing the hash
+// seeds of the attempts from `seed`.  host_keys: the same keys on the host for the duplicate check
+// after a first failed attempt, or nullptr when the keys are distinct by construction.  The peel
+// state (16 bytes per vertex) is freed on return.
+void mph_peel(const uint64_t* dkeys, uint32_t m, uint32_t seed, const uint64_t* host_keys, Bdz& h, MphPeel& S,
+              skm_mph_stats& st) {
+    DevBuf ddx, dfr0, dfr1;
+    alloc_reported(S.dpe, 4ull * m, "BDZ peel list");
+    alloc_reported(S.dpp, m, "BDZ peel positions");
+    S.dcnt.ensure(64);
+    uint32_t* cnt = S.dcnt.as<uint32_t>();  // [0] frontier A, [1] frontier B, [2] peeled, [3] bad, [4] order
+    std::mt19937 rng(seed);
+    bool ok = false;
+    std::vector<uint32_t>& rounds = S.rounds;  // peel-list boundaries
+    MphDev& P = S.P;
+    for (int attempt = 0; attempt < 1000 && !ok; ++attempt) {
+        if (attempt > 0 && attempt % 20 == 0) h.r += 2;
+        if (attempt == 1 && host_keys) {  // duplicate keys never give an acyclic graph: check once
+            SKM_HIP(hipMemset(cnt + 4, 0, 4));
+            hipLaunchKernelGGL(k_mph_adjacent, dim3(ceil_div(m, 256)), dim3(256), 0, 0, dkeys, m, cnt + 4);
+            uint32_t order = 0;
+            SKM_HIP(hipMemcpy(&order, cnt + 4, 4, hipMemcpyDeviceToHost));
+            bool dup = (order & 2u) != 0;
+            if (order & 1u) {  // not ascending: sort a host copy
+                std::vector<uint64_t> sk(host_keys, host_keys + m);
+                std::sort(sk.begin(), sk.end());
+                dup = std::adjacent_find(sk.begin(), sk.end()) != sk.end();
+            }
+            SKM_CHECK(!dup, SKM_E_ARG, "BDZ construction failed: duplicate keys");
+        }
+        h.n = 3 * h.r;
+        SKM_CHECK((uint64_t)3 * h.r < 0xFFFFF000ull, SKM_E_ARG, "BDZ vertex count exceeds 32 bits");
+        h.ranktablesize = (uint32_t)std::ceil(h.n / (double)h.k);
+        h.seed = rng();
+        P = MphDev{h.r, ~0ull / h.r + 1, h.seed};
+        const uint32_t nv = h.n;
+        alloc_reported(ddx, 8ull * nv, "BDZ peel state");
+        alloc_reported(dfr0, 4ull * nv, "BDZ frontier");
+        alloc_reported(dfr1, 4ull * nv, "BDZ frontier");
+        SKM_HIP(hipMemset(ddx.p, 0, 8ull * nv));
+        SKM_HIP(hipMemset(S.dcnt.p, 0, 64));
+        hipLaunchKernelGGL(k_mph_edges, dim3(ceil_div(m, 256)), dim3(256), 0, 0, dkeys, m, P,
+                           ddx.as<unsigned long long>(), cnt + 3);
+        hipLaunchKernelGGL(k_mph_frontier, dim3(ceil_div(nv, 256 * MPH_FR_PER)), dim3(256), 0, 0, ddx.as<unsigned long long>(), nv,
+                           dfr0.as<uint32_t>(), cnt + 0);
+        SKM_HIP(hipGetLastError());
+        uint32_t hc[4] = {0, 0, 0, 0};
+        SKM_HIP(hipMemcpy(hc, cnt, 16, hipMemcpyDeviceToHost));
+        uint32_t nf = hc[3] ? 0u : hc[0], npeeled = 0;  // a vertex of degree >= MPH_DEG_MAX: next seed
+        rounds.assign(1, 0);
+        DevBuf* cur = &dfr0;
+        DevBuf* nxt = &dfr1;
+        int fcur = 0;
+        while (nf > 0) {
+            hipLaunchKernelGGL(k_mph_peel, dim3(ceil_div(nf, 256)), dim3(256), 0, 0, cur->as<uint32_t>(), nf, dkeys, P,
+                               ddx.as<unsigned long long>(), S.dpe.as<uint32_t>(), S.dpp.as<uint8_t>(), cnt + 2);
+            SKM_HIP(hipMemset(cnt + (1 - fcur), 0, 4));
+            uint32_t np = 0;
+            SKM_HIP(hipMemcpy(&np, cnt + 2, 4, hipMemcpyDeviceToHost));
+            if (np == npeeled) break;
+            hipLaunchKernelGGL(k_mph_apply, dim3(ceil_div(np - npeeled, 256)), dim3(256), 0, 0, S.dpe.as<uint32_t>(),
+                               npeeled, np, dkeys, P, ddx.as<unsigned long long>(), nxt->as<uint32_t>(),
+                               cnt + (1 - fcur));
+            SKM_HIP(hipGetLastError());
+            rounds.push_back(np);
+            npeeled = np;
+            SKM_HIP(hipMemcpy(&nf, cnt + (1 - fcur), 4, hipMemcpyDeviceToHost));
+            std::swap(cur, nxt);
+            fcur = 1 - fcur;
+        }
+        ok = npeeled == m;
+        st.attempts = (uint32_t)attempt + 1;
+    }
+    SKM_CHECK(ok, SKM_E_ARG, "BDZ construction failed: no acyclic 3-graph in 1000 attempts");
+    st.peel_rounds = (uint32_t)rounds.size() - 1;
+    st.n_vertices = h.n;
+}
+
+// g (preset to 0xFF) from the peel list, rounds in reverse; the peel list is freed
+void mph_assign(MphPeel& S, const uint64_t* dkeys, uint32_t* g) {
+    for (size_t ri = S.rounds.size() - 1; ri >= 1; --ri) {
+        const uint32_t p0 = S.rounds[ri - 1], p1 = S.rounds[ri];
+        hipLaunchKernelGGL(k_mph_assign, dim3(ceil_div(p1 - p0, 256)), dim3(256), 0, 0, S.dpe.as<uint32_t>(),
+                           S.dpp.as<uint8_t>(), p0, p1, dkeys, S.P, g);
+    }
+    SKM_HIP(hipGetLastError());
+    S.dpe.release();  // (hipFree waits for the kernels)
+    S.dpp.release();
+}
 }  // namespace
 
 extern "C" int skm_mph_build_device_ex(const uint64_t* keys, const skm_stored_kmer_data* data, size_t nkeys,
@@ -2045,98 +2213,21 @@ extern "C" int skm_mph_build_device_ex(const uint64_t* keys, const skm_stored_km
     h.b = 7;
     h.k = 1u << h.b;
     auto t = std::chrono::steady_clock::now();
-    DevBuf dkeys, ddata, ddx, dfr0, dfr1, dpe, dpp, dcnt, dg;
+    DevBuf dkeys, ddata, dg;
     dkeys.ensure(8ull * m);
     SKM_HIP(hipMemcpy(dkeys.p, keys, 8ull * m, hipMemcpyHostToDevice));
     st.upload_s = secs_since(t);
     t = std::chrono::steady_clock::now();
-    dpe.ensure(4ull * m);
-    dpp.ensure(m);
-    dcnt.ensure(64);
-    uint32_t* cnt = dcnt.as<uint32_t>();  // [0] frontier A, [1] frontier B, [2] peeled, [3] bad, [4] order
-    std::mt19937 rng(seed);
-    bool ok = false;
-    std::vector<uint32_t> rounds;  // peel-list boundaries
-    MphDev P{};
-    for (int attempt = 0; attempt < 1000 && !ok; ++attempt) {
-        if (attempt > 0 && attempt % 20 == 0) h.r += 2;
-        if (attempt == 1) {  // duplicate keys never give an acyclic graph: check once
-            SKM_HIP(hipMemset(cnt + 4, 0, 4));
-            hipLaunchKernelGGL(k_mph_adjacent, dim3(ceil_div(m, 256)), dim3(256), 0, 0, dkeys.as<uint64_t>(), m, cnt + 4);
-            uint32_t order = 0;
-            SKM_HIP(hipMemcpy(&order, cnt + 4, 4, hipMemcpyDeviceToHost));
-            bool dup = (order & 2u) != 0;
-            if (order & 1u) {  // not ascending: sort a host copy
-                std::vector<uint64_t> sk(keys, keys + nkeys);
-                std::sort(sk.begin(), sk.end());
-                dup = std::adjacent_find(sk.begin(), sk.end()) != sk.end();
-            }
-            SKM_CHECK(!dup, SKM_E_ARG, "BDZ construction failed: duplicate keys");
-        }
-        h.n = 3 * h.r;
-        SKM_CHECK((uint64_t)3 * h.r < 0xFFFFF000ull, SKM_E_ARG, "BDZ vertex count exceeds 32 bits");
-        h.ranktablesize = (uint32_t)std::ceil(h.n / (double)h.k);
-        h.seed = rng();
-        P = MphDev{h.r, ~0ull / h.r + 1, h.seed};
-        const uint32_t nv = h.n;
-        ddx.ensure(8ull * nv);
-        dfr0.ensure(4ull * nv);
-        dfr1.ensure(4ull * nv);
-        SKM_HIP(hipMemset(ddx.p, 0, 8ull * nv));
-        SKM_HIP(hipMemset(dcnt.p, 0, 64));
-        hipLaunchKernelGGL(k_mph_edges, dim3(ceil_div(m, 256)), dim3(256), 0, 0, dkeys.as<uint64_t>(), m, P,
-                           ddx.as<unsigned long long>(), cnt + 3);
-        hipLaunchKernelGGL(k_mph_frontier, dim3(ceil_div(nv, 256 * MPH_FR_PER)), dim3(256), 0, 0, ddx.as<unsigned long long>(), nv,
-                           dfr0.as<uint32_t>(), cnt + 0);
-        SKM_HIP(hipGetLastError());
-        uint32_t hc[4] = {0, 0, 0, 0};
-        SKM_HIP(hipMemcpy(hc, cnt, 16, hipMemcpyDeviceToHost));
-        uint32_t nf = hc[3] ? 0u : hc[0], npeeled = 0;  // a vertex of degree >= MPH_DEG_MAX: next seed
-        rounds.assign(1, 0);
-        DevBuf* cur = &dfr0;
-        DevBuf* nxt = &dfr1;
-        int fcur = 0;
-        while (nf > 0) {
-            hipLaunchKernelGGL(k_mph_peel, dim3(ceil_div(nf, 256)), dim3(256), 0, 0, cur->as<uint32_t>(), nf,
-                               dkeys.as<uint64_t>(), P, ddx.as<unsigned long long>(), dpe.as<uint32_t>(),
-                               dpp.as<uint8_t>(), cnt + 2);
-            SKM_HIP(hipMemset(cnt + (1 - fcur), 0, 4));
-            uint32_t np = 0;
-            SKM_HIP(hipMemcpy(&np, cnt + 2, 4, hipMemcpyDeviceToHost));
-            if (np == npeeled) break;
-            hipLaunchKernelGGL(k_mph_apply, dim3(ceil_div(np - npeeled, 256)), dim3(256), 0, 0, dpe.as<uint32_t>(),
-                               npeeled, np, dkeys.as<uint64_t>(), P, ddx.as<unsigned long long>(),
-                               nxt->as<uint32_t>(), cnt + (1 - fcur));
-            SKM_HIP(hipGetLastError());
-            rounds.push_back(np);
-            npeeled = np;
-            SKM_HIP(hipMemcpy(&nf, cnt + (1 - fcur), 4, hipMemcpyDeviceToHost));
-            std::swap(cur, nxt);
-            fcur = 1 - fcur;
-        }
-        ok = npeeled == m;
-        st.attempts = (uint32_t)attempt + 1;
-    }
-    SKM_CHECK(ok, SKM_E_ARG, "BDZ construction failed: no acyclic 3-graph in 1000 attempts");
-    st.peel_rounds = (uint32_t)rounds.size() - 1;
-    st.n_vertices = h.n;
-    ddx.release();
-    dfr0.release();
-    dfr1.release();
+    MphPeel S;
+    mph_peel(dkeys.as<uint64_t>(), m, seed, keys, h, S, st);
+    uint32_t* cnt = S.dcnt.as<uint32_t>();
     st.peel_s = secs_since(t);
     // assignment, rounds in reverse
     t = std::chrono::steady_clock::now();
     const uint64_t gwords = ceil_div(h.n, 16) + 1;
     dg.ensure(4 * gwords);
     SKM_HIP(hipMemset(dg.p, 0xFF, 4 * gwords));
-    for (size_t ri = rounds.size() - 1; ri >= 1; --ri) {
-        const uint32_t p0 = rounds[ri - 1], p1 = rounds[ri];
-        hipLaunchKernelGGL(k_mph_assign, dim3(ceil_div(p1 - p0, 256)), dim3(256), 0, 0, dpe.as<uint32_t>(),
-                           dpp.as<uint8_t>(), p0, p1, dkeys.as<uint64_t>(), P, dg.as<uint32_t>());
-    }
-    SKM_HIP(hipGetLastError());
-    dpe.release();
-    dpp.release();
+    mph_assign(S, dkeys.as<uint64_t>(), dg.as<uint32_t>());
     std::vector<uint32_t> gw(gwords);
     SKM_HIP(hipMemcpy(gw.data(), dg.p, 4 * gwords, hipMemcpyDeviceToHost));
     st.assign_s = secs_since(t);
@@ -2179,7 +2270,7 @@ extern "C" int skm_mph_build_device_ex(const uint64_t* keys, const skm_stored_km
     D.r_magic = ~0ull / h.r + 1;
     SKM_HIP(hipMemset(cnt + 3, 0, 4));
     hipLaunchKernelGGL(k_mph_place, dim3(ceil_div(m, 256)), dim3(256), 0, 0, dkeys.as<uint64_t>(), m, D,
-                       ddata.as<uint16_t>(), ddat.as<uint16_t>(), verify ? dbits.as<uint32_t>() : nullptr, cnt + 3);
+                       ddata.as<uint16_t>(), ddat.as<uint16_t>(), nullptr, verify ? dbits.as<uint32_t>() : nullptr, cnt + 3);
     SKM_HIP(hipGetLastError());
     uint32_t bad = 0;
     SKM_HIP(hipMemcpy(&bad, cnt + 3, 4, hipMemcpyDeviceToHost));
@@ -2205,18 +2296,215 @@ extern "C" int skm_mph_build_device_ex(const uint64_t* keys, const skm_stored_km
         st.verify_s = secs_since(t);
     }
     t = std::chrono::steady_clock::now();
-    if (mph_path) {
-        std::vector<uint8_t> img = bdz_dump(h);
-        std::ofstream fm(mph_path, std::ios::binary);
-        SKM_CHECK((bool)fm, SKM_E_IO, std::string("cannot write ") + mph_path);
-        fm.write((const char*)img.data(), (std::streamsize)img.size());
-        SKM_CHECK((bool)fm, SKM_E_IO, "write failed");
-    }
+    if (mph_path) write_mph_image(mph_path, h);
     if (dat_path)
         SKM_CHECK(write_device_file(dat_path, ddat.p, 10ull * m, device), SKM_E_IO, std::string("cannot write ") + dat_path);
     st.write_s = secs_since(t);
     st.total_s = secs_since(t_all);
     if (stats) *stats = st;
+    SKM_API_END
+}
+
+namespace skm {
+
+// g as the DB holds it: ceil(n / 4) bytes padded with 0xFF to a multiple of 64, plus one line
+// (db_upload's padding)
+static uint64_t db_g_bytes(uint64_t nv) { return ((ceil_div(nv, 4) + 63) / 64) * 64 + 64; }
+
+void mph_db_plan(uint64_t n, uint64_t out[4]) {
+    SKM_CHECK(n <= MPH_MAX_KEYS, SKM_E_ARG,
+              "too many keys for one BDZ: cmph keeps m, n = 3r as 32-bit words (n = 1.23 m < 2^32)");
+    uint64_t r = (uint64_t)std::ceil((1.23 * (double)n) / 3);
+    if (r % 2 == 0) r += 1;
+    const uint64_t nv = 3 * r;
+    // the open DB: g, the rank table, the records, the record words, the pair lines
+    const uint64_t db = db_g_bytes(nv) + 4 * std::max<uint64_t>(ceil_div(nv, 128), 1) + std::max<uint64_t>(10 * n, 16) +
+                        4 * std::max<uint64_t>(n, 1) + 64 * (nv / 128 + 2);
+    // the peel: degree / edge-sum word and two frontiers per vertex, the peel list and its positions
+    // per key, the counters; everything of it is gone before the first array of the DB but g
+    const uint64_t peel = 16 * nv + 5 * n + 64;
+    // placing: the DB, the tile sums of the rank scan, the slot bitmap of verify
+    const uint64_t place = db + 8 * ceil_div(ceil_div(nv, 128), MPH_RANK_TILE) + 8 + 4 * (ceil_div(n, 32) + 1) + 64;
+    out[0] = r;
+    out[1] = nv;
+    out[2] = db;
+    out[3] = std::max(n < 1024 ? 0 : peel, place);
+}
+
+skm_db* db_from_host_mph(const uint64_t* keys, const skm_stored_kmer_data* data, uint64_t n, const skm_mph_db_opts* o,
+                         int device, skm_mph_stats* stats) {
+    const auto t_all = std::chrono::steady_clock::now();
+    skm_mph_stats st{};
+    st.n_keys = n;
+    Bdz h;
+    std::string err;
+    SKM_CHECK(bdz_build(keys, n, o->seed, h, err), SKM_E_ARG, err);
+    st.n_vertices = h.n;
+    std::vector<skm_stored_kmer_data> kd(n);
+    std::vector<uint8_t> seen(n, 0);
+    std::vector<uint32_t> slot(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint8_t kb[8];
+        std::memcpy(kb, &keys[i], 8);
+        const uint32_t idx = slot[i] = bdz_search(h, kb, 8);
+        SKM_CHECK(idx < n, SKM_E_ARG, "BDZ construction produced an out-of-range slot");
+        SKM_CHECK(!seen[idx], SKM_E_STATE, "BDZ construction mapped two keys to one slot");
+        seen[idx] = 1;
+        kd[idx] = data[i];
+    }
+    const std::vector<uint8_t> img = bdz_dump(h);
+    skm_db* raw = nullptr;
+    const int rc = skm_db_open_mem(&raw, img.data(), img.size(), reinterpret_cast<const uint8_t*>(kd.data()), 10 * n, device);
+    if (rc) throw Error(rc, skm_last_error());
+    std::unique_ptr<skm_db, void (*)(skm_db*)> db(raw, skm_db_close);
+    if (o->verify) {  // the slots are a permutation (above); both device searches against the host's
+        const auto tv = std::chrono::steady_clock::now();
+        std::vector<uint32_t> a(n), g(n);
+        if (n) {
+            int rv = skm_db_lookup(raw, keys, n, a.data());
+            if (!rv) rv = skm_debug_db_lookup_generic(raw, keys, n, g.data());
+            if (rv) throw Error(rv, skm_last_error());
+        }
+        SKM_CHECK(g == slot, SKM_E_STATE, "BDZ device search differs from the host search");
+        SKM_CHECK(a == g, SKM_E_STATE, "BDZ pair-line search differs from the generic search");
+        st.verified = 1;
+        st.verify_s = secs_since(tv);
+    }
+    const auto t = std::chrono::steady_clock::now();
+    if (o->mph_path) write_mph_image(o->mph_path, h);
+    if (o->dat_path) {
+        std::ofstream fd(o->dat_path, std::ios::binary);
+        SKM_CHECK((bool)fd, SKM_E_IO, std::string("cannot write ") + o->dat_path);
+        if (n) fd.write((const char*)kd.data(), (std::streamsize)(10 * n));
+        SKM_CHECK((bool)fd, SKM_E_IO, "write failed");
+    }
+    st.write_s = secs_since(t);
+    st.total_s = secs_since(t_all);
+    if (stats) *stats = st;
+    return db.release();
+}
+
+skm_db* db_from_device_mph(const uint64_t* d_keys, const skm_stored_kmer_data* d_data, uint64_t n,
+                           const skm_mph_db_opts* o, int device, skm_mph_stats* stats) {
+    SKM_CHECK(n >= 1024 && n <= MPH_MAX_KEYS, SKM_E_ARG, "bad BDZ DB size");
+    SKM_HIP(hipSetDevice(device));
+    const auto t_all = std::chrono::steady_clock::now();
+    skm_mph_stats st{};
+    st.n_keys = n;
+    const uint32_t m = (uint32_t)n;
+    Bdz h;  // the geometry; g and the rank table are filled only for the dump
+    h.m = m;
+    h.r = (uint32_t)std::ceil((1.23 * m) / 3);
+    if (h.r % 2 == 0) h.r += 1;
+    h.b = 7;
+    h.k = 1u << h.b;
+    std::unique_ptr<skm_db, void (*)(skm_db*)> db(new skm_db(), skm_db_close);
+    db->device = device;
+    // peel: the arena's keys in place
+    auto t = std::chrono::steady_clock::now();
+    MphPeel S;
+    mph_peel(d_keys, m, o->seed, nullptr, h, S, st);
+    uint32_t* cnt = S.dcnt.as<uint32_t>();
+    st.peel_s = secs_since(t);
+    // assignment, rounds in reverse, into the DB's g
+    t = std::chrono::steady_clock::now();
+    const uint64_t gbytes = db_g_bytes(h.n), gwords = gbytes / 4;
+    alloc_reported(db->d_g, gbytes, "BDZ g");
+    SKM_HIP(hipMemset(db->d_g.p, 0xFF, gbytes));
+    mph_assign(S, d_keys, db->d_g.as<uint32_t>());
+    st.assign_s = secs_since(t);
+    // the rank table: assigned vertices per 128-vertex block, scanned
+    t = std::chrono::steady_clock::now();
+    const uint32_t nrank = h.ranktablesize;
+    const uint64_t ntile = ceil_div(nrank, MPH_RANK_TILE);
+    alloc_reported(db->d_rank, 4ull * nrank, "BDZ rank table");
+    {
+        DevBuf dtiles;  // [ntile] tile counts, then offsets; [ntile] = the total
+        dtiles.ensure(8 * (ntile + 1));
+        const dim3 grid((uint32_t)ceil_div(nrank, 256)), blk(256);
+        hipLaunchKernelGGL(k_mph_rank_tiles, grid, blk, 0, 0, db->d_g.as<uint32_t>(), gwords, nrank, dtiles.as<uint64_t>());
+        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, 0, dtiles.as<uint64_t>(), ntile, dtiles.as<uint64_t>() + ntile);
+        hipLaunchKernelGGL(k_mph_rank_write, grid, blk, 0, 0, db->d_g.as<uint32_t>(), gwords, nrank, dtiles.as<uint64_t>(),
+                           db->d_rank.as<uint32_t>());
+        SKM_HIP(hipGetLastError());
+        uint64_t count = 0;
+        SKM_HIP(hipMemcpy(&count, dtiles.as<uint64_t>() + ntile, 8, hipMemcpyDeviceToHost));
+        SKM_CHECK(count == m, SKM_E_ARG, "BDZ construction: assigned vertex count != number of keys");
+    }
+    st.rank_s = secs_since(t);
+    // place the records, and their record words, into the DB's own arrays: dat[search(key)] = data
+    t = std::chrono::steady_clock::now();
+    alloc_reported(db->d_dat, 10ull * m, "BDZ records");
+    alloc_reported(db->d_fm, 4ull * m, "BDZ record words");
+    const uint64_t nblk = (uint64_t)h.n / 128 + 2;
+    alloc_reported(db->d_blk, 64 * nblk, "BDZ pair lines");
+    DevBuf dbits;
+    if (o->verify) {
+        alloc_reported(dbits, 4 * (ceil_div(m, 32) + 1), "BDZ slot bitmap");
+        SKM_HIP(hipMemset(dbits.p, 0, 4 * (ceil_div(m, 32) + 1)));
+    }
+    DevBdz& D = db->dev;
+    D = DevBdz{};
+    D.g = db->d_g.as<uint32_t>();
+    D.ranktable = db->d_rank.as<uint32_t>();
+    D.dat = db->d_dat.as<uint16_t>();
+    D.fm = db->d_fm.as<uint32_t>();
+    D.m = m;
+    D.r = h.r;
+    D.b = h.b;
+    D.seed = h.seed;
+    D.r_magic = ~0ull / h.r + 1;
+    db->m = m;
+    db->dat_records = m;
+    const uint16_t* data16 = reinterpret_cast<const uint16_t*>(d_data);
+    SKM_HIP(hipMemset(cnt + 3, 0, 4));
+    hipLaunchKernelGGL(k_mph_place, dim3(ceil_div(m, 256)), dim3(256), 0, 0, d_keys, m, D, data16, db->d_dat.as<uint16_t>(),
+                       db->d_fm.as<uint32_t>(), o->verify ? dbits.as<uint32_t>() : nullptr, cnt + 3);
+    hipLaunchKernelGGL(k_mph_blk, dim3((uint32_t)ceil_div(nblk, 256)), dim3(256), 0, 0, db->d_g.as<uint32_t>(), gwords,
+                       db->d_rank.as<uint32_t>(), (uint64_t)nrank, nblk, db->d_blk.as<uint32_t>());
+    SKM_HIP(hipGetLastError());
+    D.blk = db->d_blk.as<uint32_t>();
+    uint32_t bad = 0;
+    SKM_HIP(hipMemcpy(&bad, cnt + 3, 4, hipMemcpyDeviceToHost));
+    SKM_CHECK(!(bad & 1u), SKM_E_ARG, "BDZ construction produced an out-of-range slot");
+    SKM_CHECK(!(bad & 2u), SKM_E_STATE, "BDZ construction mapped two keys to one slot");
+    st.place_s = secs_since(t);
+    if (o->verify) {  // the pair-line search over every key against the generic one, and the records
+        t = std::chrono::steady_clock::now();
+        dbits.release();
+        hipLaunchKernelGGL(k_mph_verify, dim3(ceil_div(m, 256)), dim3(256), 0, 0, d_keys, m, D, data16,
+                           db->d_dat.as<uint16_t>(), cnt + 3);
+        SKM_HIP(hipGetLastError());
+        SKM_HIP(hipMemcpy(&bad, cnt + 3, 4, hipMemcpyDeviceToHost));
+        SKM_CHECK(!(bad & 4u), SKM_E_STATE, "BDZ pair-line search differs from the generic search");
+        SKM_CHECK(!(bad & 8u), SKM_E_STATE, "BDZ .dat record differs from its key's record");
+        st.verified = 1;
+        st.verify_s = secs_since(t);
+    }
+    t = std::chrono::steady_clock::now();
+    if (o->mph_path) {  // the only use of g and the rank table on the host
+        h.g.resize(ceil_div(h.n, 4));
+        h.ranktable.resize(nrank);
+        SKM_HIP(hipMemcpy(h.g.data(), db->d_g.p, h.g.size(), hipMemcpyDeviceToHost));
+        SKM_HIP(hipMemcpy(h.ranktable.data(), db->d_rank.p, 4ull * nrank, hipMemcpyDeviceToHost));
+        write_mph_image(o->mph_path, h);
+    }
+    if (o->dat_path)
+        SKM_CHECK(write_device_file(o->dat_path, db->d_dat.p, 10ull * m, device), SKM_E_IO,
+                  std::string("cannot write ") + o->dat_path);
+    SKM_HIP(hipDeviceSynchronize());
+    st.write_s = secs_since(t);
+    st.total_s = secs_since(t_all);
+    if (stats) *stats = st;
+    return db.release();
+}
+
+}  // namespace skm
+
+extern "C" int skm_mph_db_plan(uint64_t n, uint64_t out[4]) {
+    SKM_API_BEGIN
+    SKM_CHECK(out, SKM_E_ARG, "null argument");
+    mph_db_plan(n, out);
     SKM_API_END
 }
 

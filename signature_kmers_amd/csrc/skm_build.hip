@@ -39,6 +39,7 @@
 
 #include "skm_common.h"
 #include "skm_keptdb.h"
+#include "skm_mphdb.h"
 #include "skm_pool.h"
 #include "skm_output.h"
 #include "skm_util.h"
@@ -8142,6 +8143,39 @@ int skm_build_kept_db(skm_build* b, const skm_kept_db_opts* opts, skm_db** out) 
     if (opts && opts->release_work && !b->work_released) release_work(b);
     *out = db_from_device_kept(b->d_keys.as<uint64_t>(), b->d_data.as<skm_stored_kmer_data>(), b->n_kept, slots,
                                b->device, b->stream);
+    SKM_API_END
+}
+
+int skm_build_mph_db(skm_build* b, const skm_mph_db_opts* opts, skm_db** out, skm_mph_stats* stats) {
+    SKM_API_BEGIN
+    SKM_CHECK(b && out, SKM_E_ARG, "null argument");
+    *out = nullptr;
+    SKM_CHECK(b->world == 1, SKM_E_STATE,
+              "skm_build_mph_db needs world_size 1: the kept set of a multi-rank build is sharded over the ranks");
+    skm_mph_db_opts o{};
+    o.seed = 1;
+    if (opts) o = *opts;
+    SKM_HIP(hipSetDevice(b->device));
+    if (!b->prepared || !b->ran) run_ranks(Ranks{b});
+    uint64_t plan[4];
+    mph_db_plan(b->n_kept, plan);  // more kept k-mers than one BDZ holds: SKM_E_ARG
+    if (o.release_work && !b->work_released) release_work(b);
+    if (b->n_kept < 1024) {  // skm_mph_build_device's small-size rule: the host builder over the sorted kept set
+        skm_kept kept{};
+        const int rc = skm_build_finish(b, &kept);
+        if (rc) return rc;
+        try {
+            *out = db_from_host_mph(kept.keys, kept.data, kept.n, &o, b->device, stats);
+        } catch (...) {
+            skm_kept_free(&kept);
+            throw;
+        }
+        skm_kept_free(&kept);
+        return SKM_OK;
+    }
+    SKM_HIP(hipDeviceSynchronize());  // nothing of the run in flight: the arena is read on the null stream
+    *out = db_from_device_mph(b->d_keys.as<uint64_t>(), b->d_data.as<skm_stored_kmer_data>(), b->n_kept, &o, b->device,
+                              stats);
     SKM_API_END
 }
 

@@ -11,7 +11,10 @@
 // ascending function index; the reference writes both in TBB hash-table order, so compare them
 // as sets.  --nudb-file is not supported (NuDB is out of scope).
 // Extra options: --device N (HIP device), --dump-extract FILE (write the build input arrays and
-// stop before touching the GPU; used by the CPU tests), --mph-seed N.
+// stop before touching the GPU; used by the CPU tests), --mph-seed N, --recall-db host|device (the
+// recall DB from the downloaded kept k-mers, or built on the GPU from the resident ones),
+// --perfect-hash-source host|device (likewise for kmer_data.mph / .dat: skm_build_mph_db; the files
+// are the same).
 // Multi-GPU: --n-gpus N forks one process per GPU (rank r on device r) before
 // any GPU or thread use; or, under an external launcher (RANK / WORLD_SIZE / LOCAL_RANK in the
 // environment, e.g. torchrun --no-python), each launched process is one rank and rank 0 hands the
@@ -175,7 +178,8 @@ int main(int argc, char** argv) {
                 {"help", 'h', true, false},            {"device", 0, false, false},
                 {"dump-extract", 0, false, false},     {"mph-seed", 0, false, false},
                 {"n-gpus", 0, false, false},           {"comm", 0, false, false},
-                {"comm-file", 0, false, false},        {"recall-db", 0, false, false}};
+                {"comm-file", 0, false, false},        {"recall-db", 0, false, false},
+                {"perfect-hash-source", 0, false, false}};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
     if (op.has("help")) {
@@ -199,6 +203,9 @@ int main(int argc, char** argv) {
                   << "  --comm-file arg                      RCCL id rendezvous file under an external launcher\n"
                   << "  --recall-db arg                      host (default): the recall DB from the downloaded kept k-mers;\n"
                   << "                                       device: built on the GPU from the build's resident kept k-mers (one GPU)\n"
+                  << "  --perfect-hash-source arg            host (default): the perfect hash from the downloaded kept k-mers;\n"
+                  << "                                       device: hash and data files written from the DB built on the GPU\n"
+                  << "                                       from the build's resident kept k-mers (needs --perfect-hash, one GPU)\n"
                   << "  -h [ --help ]                        show this help message\n";
         return 1;
     }
@@ -214,6 +221,12 @@ int main(int argc, char** argv) {
     const bool launched = env_ws && std::atoi(env_ws) > 1 && !op.has("n-gpus");
     if (recall_db == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
         die("--recall-db device needs one GPU: the kept k-mers of a multi-rank build are sharded over the ranks");
+    const std::string ph_source = op.get("perfect-hash-source", "host");
+    if (ph_source != "host" && ph_source != "device") die("--perfect-hash-source must be host or device");
+    if (ph_source == "device" && op.get("perfect-hash").empty())
+        die("--perfect-hash-source device needs --perfect-hash: it names the file the hash is written to");
+    if (ph_source == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
+        die("--perfect-hash-source device needs one GPU: the kept k-mers of a multi-rank build are sharded over the ranks");
     int local_rank = 0;
     if (launched) {
         if (comm == "host") die("--comm host needs --n-gpus (forked ranks)");
@@ -238,6 +251,11 @@ int main(int argc, char** argv) {
     const std::string kmer_data_dir = op.get("kmer-data-dir");
     std::string final_kmers = op.get("final-kmers");
     std::string ph_file = op.get("perfect-hash"), ph_data = op.get("perfect-hash-data");
+    if (!ph_file.empty()) {
+        if (path_is_relative(ph_file)) ph_file = path_join(kmer_data_dir, ph_file);
+        if (path_is_relative(ph_data)) ph_data = path_join(kmer_data_dir, ph_data);
+    }
+    const uint32_t mph_seed = (uint32_t)std::strtoul(op.get("mph-seed", "1").c_str(), nullptr, 10);
 
     // the HIP runtime initialises on a thread of its own while the host parses (the first HIP call
     // of a process costs ~0.3-0.5 s)
@@ -438,6 +456,24 @@ int main(int argc, char** argv) {
     float ph[12] = {0};
     int nph = skm_build_last_timings(b, ph, 12);
     const double t_build = t_prepare + t_run + t_finish;
+    // --perfect-hash-source device: the hash and its data file from the arena while the handle still
+    // holds it; its DB is closed before the recall table is allocated (the peel state and that table
+    // are the two largest transients)
+    double t_mph = 0;
+    if (ph_source == "device") {
+        const double tm = now_s();
+        std::cerr << "build perfect hash into " << quoted(ph_file) << " with data in " << quoted(ph_data) << "\n";
+        skm_mph_db_opts mo{};
+        mo.seed = mph_seed;
+        mo.release_work = 1;
+        mo.mph_path = ph_file.c_str();
+        mo.dat_path = ph_data.c_str();
+        skm_db* mdb = nullptr;
+        check(skm_build_mph_db(b, &mo, &mdb, nullptr), "skm_build_mph_db");
+        skm_db_close(mdb);
+        t_mph = now_s() - tm;
+        std::cerr << "Wrote " << kept.n << " values\n";
+    }
     // --recall-db device: the recall DB from the arena while the handle still holds it (the work
     // buffers go first: the table needs their room at the headline size)
     skm_db* kdb = nullptr;
@@ -456,7 +492,7 @@ int main(int argc, char** argv) {
     std::cout << "num_seqs_with_a_signature=" << kept.n_seqs_with_signature << "\n";
 
     std::thread final_kmers_thread;
-    double t_final_kmers = 0, t_mph = 0;
+    double t_final_kmers = 0;
     if (!final_kmers.empty()) {
         if (path_is_relative(final_kmers)) {
             final_kmers = path_join(kmer_data_dir, final_kmers);
@@ -484,10 +520,8 @@ int main(int argc, char** argv) {
     std::thread perfect_hash_thread;
     int ph_rc = 0;
     std::string ph_err;
-    if (!ph_file.empty()) {
-        if (path_is_relative(ph_file)) ph_file = path_join(kmer_data_dir, ph_file);
-        if (path_is_relative(ph_data)) ph_data = path_join(kmer_data_dir, ph_data);
-        const uint32_t seed = (uint32_t)std::strtoul(op.get("mph-seed", "1").c_str(), nullptr, 10);
+    if (!ph_file.empty() && ph_source == "host") {
+        const uint32_t seed = mph_seed;
         perfect_hash_thread = std::thread([&, seed]() {
             const double tm = now_s();
             std::cerr << "build perfect hash into " << quoted(ph_file) << " with data in " << quoted(ph_data) << "\n";
