@@ -506,6 +506,55 @@ int skm_annotate(skm_db* db, const uint8_t* residues, const uint64_t* seq_off, c
 void skm_calls_free(skm_calls* c);
 
 /* ------------------------------------------------------------------------------------------
+ * FASTA parsed on the device: raw file bytes in, a resident query out.  Replaces FastaParser
+ * (fasta_parser.h:38-144, fasta_parser.cc:17-36) for the sequence bodies, and the per-record
+ * copies of FunctionCaller::process_fasta_stream (call_functions.tcc:217-255): the packed
+ * residues, the per-sequence table and the window offsets are built in HBM.  Ids and definition
+ * lines stay host string work (the headers-only host parse).
+ *
+ * bytes[0, file_off[n_files]) = the files back to back, file f at [file_off[f], file_off[f+1])
+ * (file_off ascends from 0; empty files allowed).  Every file is parsed as the reference parses
+ * it: '\r' dropped in every state, bytes before the first '>' and every byte the reference reports
+ * as an error dropped, a record ended by a '>' at a line start or by the end of its file
+ * (parse_complete()), a record with an empty id dropped with its residues -- as every caller of
+ * the reference skips it (signature_build.tcc:124).  Error reports are not made here.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct skm_fasta_table {
+    uint64_t n_files, n_recs, n_residues, n_windows;
+    uint64_t* file_rec;   /* [n_files+1] first kept record of each file; [n_files] = n_recs  */
+    uint32_t* seq_len;    /* [n_recs]                                                       */
+    uint64_t* hdr_pos;    /* [n_recs] position in bytes[] of the record's '>'               */
+    uint8_t*  residues;   /* packed (record s at sum over t < s of (seq_len[t] + 1), a 0    */
+                          /* after each), only when asked for (tests, diagnostics); else NULL */
+    float parse_ms;       /* device time of the parse                                       */
+} skm_fasta_table;
+
+/* The device parser's chunk geometry (fasta_parser.h:38-144 has none: it is a byte loop): bytes
+ * per thread per step, bytes per wave per step, bytes per workgroup tile, reserved (0). */
+int skm_fasta_parse_info(uint32_t out[4]);
+/* FastaParser::parse + parse_complete (fasta_parser.h:38-144, fasta_parser.cc:17-36) over every
+ * file, on `device`: the table of the kept records (*out is overwritten; release it with
+ * skm_fasta_table_free).  SKM_E_ARG: a null array, a file_off that does not ascend from 0,
+ * >= 2^32 - 1 kept records, a record longer than 2^32 - 2 residues. */
+int skm_fasta_parse_device(const uint8_t* bytes, const uint64_t* file_off, size_t n_files, int device,
+                           int want_residues, skm_fasta_table* out);
+/* skm_query_create from file bytes (FastaParser, fasta_parser.h:38-144, feeding process_aa_seq as
+ * process_fasta_stream does, call_functions.tcc:217-255): parses straight into the query's own
+ * device buffers (no second device copy of the residues; the raw bytes live in a buffer of the
+ * query that only grows).  The result is an ordinary skm_query: query s is kept record s.  tab
+ * (optional, overwritten) gets the table, without residues. */
+int skm_query_create_fasta(skm_query** out, skm_db* db, const uint8_t* bytes, const uint64_t* file_off,
+                           size_t n_files, skm_fasta_table* tab);
+/* skm_annotate from file bytes (process_fasta_stream, call_functions.tcc:217-255, with FastaParser,
+ * fasta_parser.h:38-144, on the device): parse + run + calls through the query object the DB keeps
+ * for skm_annotate; a later skm_annotate on the same DB is unaffected. */
+int skm_annotate_fasta(skm_db* db, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                       const skm_annot_opts* opts, skm_calls* calls, skm_fasta_table* tab);
+/* Releases the arrays of a table filled by the three calls above (fasta_parser.h:38-144 has no
+ * counterpart: its records are std::strings). */
+void skm_fasta_table_free(skm_fasta_table* t);
+
+/* ------------------------------------------------------------------------------------------
  * All-vs-all shared-signature-k-mer counts.  Replaces MatrixDistance::compute
  * (matrix_distance.h:45-170) as run by kmers-matrix-distance (kmers-matrix-distance.cc:94-212):
  * process_aa_seq with ignore_hypothetical(true) feeds hit_cb (:123-152: hits whose seqlen lies

@@ -69,6 +69,12 @@ class _Calls(C.Structure):
                 ("n_calls", C.c_uint64), ("n_windows", C.c_uint64)]
 
 
+class _FastaTable(C.Structure):
+    _fields_ = [("n_files", C.c_uint64), ("n_recs", C.c_uint64), ("n_residues", C.c_uint64), ("n_windows", C.c_uint64),
+                ("file_rec", C.POINTER(C.c_uint64)), ("seq_len", C.POINTER(C.c_uint32)),
+                ("hdr_pos", C.POINTER(C.c_uint64)), ("residues", C.POINTER(C.c_uint8)), ("parse_ms", C.c_float)]
+
+
 class _MatrixOpts(C.Structure):
     _fields_ = [("hypo_index", C.c_int32), ("row_begin", C.c_uint32), ("row_end", C.c_uint32), ("pad", C.c_uint32),
                 ("max_tile_bytes", C.c_uint64)]
@@ -151,6 +157,12 @@ _SIGS = {
     "skm_query_destroy": (None, [_P]),
     "skm_annotate": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(_AnnotOpts), C.POINTER(_Calls)]),
     "skm_calls_free": (None, [C.POINTER(_Calls)]),
+    "skm_fasta_parse_info": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "skm_fasta_parse_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, C.POINTER(_FastaTable)]),
+    "skm_query_create_fasta": (C.c_int, [C.POINTER(_P), _P, _P, _P, C.c_size_t, C.POINTER(_FastaTable)]),
+    "skm_annotate_fasta": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(_AnnotOpts), C.POINTER(_Calls),
+                                     C.POINTER(_FastaTable)]),
+    "skm_fasta_table_free": (None, [C.POINTER(_FastaTable)]),
     "skm_matrix_create": (C.c_int, [C.POINTER(_P), _P, _P, _P, _P, _P, C.c_size_t, C.c_uint32]),
     "skm_matrix_run": (C.c_int, [_P, C.POINTER(_MatrixOpts)]),
     "skm_matrix_set_transport": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_Transport)]),
@@ -755,9 +767,76 @@ def read_function_index(path: str) -> list:
     return out
 
 
+def fasta_parse_info() -> tuple:
+    """skm_fasta_parse_info: the device FASTA parser's (bytes per thread step, bytes per wave step,
+    bytes per workgroup tile)."""
+    out = (C.c_uint32 * 4)()
+    _check(lib().skm_fasta_parse_info(out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def _fasta_input(blobs):
+    """The files of a device parse as (bytes u8, file_off u64[n_files + 1]): a sequence of
+    bytes-like objects laid back to back, or such a pair as it is."""
+    if isinstance(blobs, tuple) and len(blobs) == 2 and isinstance(blobs[0], np.ndarray):
+        return (np.ascontiguousarray(blobs[0], dtype=np.uint8), np.ascontiguousarray(blobs[1], dtype=np.uint64))
+    off = np.zeros(len(blobs) + 1, np.uint64)
+    if len(blobs):
+        off[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
+    return np.frombuffer(b"".join(bytes(b) for b in blobs), dtype=np.uint8), off
+
+
+class FastaTable:
+    """skm_fasta_table: the kept records (non-empty id) of a device FASTA parse -- file_rec
+    [n_files + 1], seq_len [n_recs], hdr_pos [n_recs] (the position of each record's '>'), the
+    totals, the parse's device ms and, when asked for, the packed residues."""
+
+    def __init__(self, t: "_FastaTable"):
+        nf, nr = int(t.n_files), int(t.n_recs)
+        self.n_files, self.n_recs = nf, nr
+        self.n_residues, self.n_windows = int(t.n_residues), int(t.n_windows)
+        self.parse_ms = float(t.parse_ms)
+        self.file_rec = np.ctypeslib.as_array(t.file_rec, shape=(nf + 1,)).copy()
+        self.seq_len = np.ctypeslib.as_array(t.seq_len, shape=(nr,)).copy() if nr else np.zeros(0, np.uint32)
+        self.hdr_pos = np.ctypeslib.as_array(t.hdr_pos, shape=(nr,)).copy() if nr else np.zeros(0, np.uint64)
+        rp = self.n_residues + nr
+        self.residues = None
+        if t.residues:
+            self.residues = np.ctypeslib.as_array(t.residues, shape=(rp,)).copy() if rp else np.zeros(0, np.uint8)
+
+
+def fasta_parse_device(blobs, device: int = 0, want_residues: bool = False) -> FastaTable:
+    """skm_fasta_parse_device: FastaParser (fasta_parser.h:38-144) over the files' bytes on the
+    device; blobs as _fasta_input takes them."""
+    data, off = _fasta_input(blobs)
+    t = _FastaTable()
+    _check(lib().skm_fasta_parse_device(_ptr(data), _ptr(off), len(off) - 1, device, int(want_residues), C.byref(t)))
+    try:
+        return FastaTable(t)
+    finally:
+        lib().skm_fasta_table_free(C.byref(t))
+
+
 class QueryBatch:
     """A batch of query sequences resident in HBM (skm_query_*): run() repeats the device pipeline
     (window lookup + HitSet calls) without re-uploading; timings() = the last run's device ms."""
+
+    @classmethod
+    def from_fasta(cls, db: "CmphKmerDb", blobs) -> "QueryBatch":
+        """skm_query_create_fasta: the queries are the kept records of the files' bytes, parsed on
+        the device; .table is their FastaTable."""
+        data, off = _fasta_input(blobs)
+        q = cls.__new__(cls)
+        q._h = C.c_void_p()
+        q.db = db
+        t = _FastaTable()
+        _check(lib().skm_query_create_fasta(C.byref(q._h), db._h, _ptr(data), _ptr(off), len(off) - 1, C.byref(t)))
+        try:
+            q.table = FastaTable(t)
+        finally:
+            lib().skm_fasta_table_free(C.byref(t))
+        q._n_seqs = q.table.n_recs
+        return q
 
     def __init__(self, db: CmphKmerDb, residues, seq_off, seq_len):
         self._h = C.c_void_p()
@@ -864,6 +943,29 @@ class FunctionCaller:
             return off, calls
         finally:
             lib().skm_calls_free(C.byref(out))
+
+    def process_fasta(self, blobs):
+        """process_fasta_stream's device half (call_functions.tcc:217-255) from the files' bytes
+        (skm_annotate_fasta: FastaParser on the device, then process_aa_seq per kept record):
+        returns (file_rec, seq_len, hdr_pos, call_off, calls); self.last_fasta is the FastaTable."""
+        if self.hypo_index < 0:  # call_functions.tcc:269-274 exits the process
+            raise SkmError("Cannot find hypothetical protein index")
+        data, foff = _fasta_input(blobs)
+        out = _Calls()
+        t = _FastaTable()
+        opts = self._opts()
+        _check(lib().skm_annotate_fasta(self.db._h, _ptr(data), _ptr(foff), len(foff) - 1, C.byref(opts), C.byref(out),
+                                        C.byref(t)))
+        try:
+            tab = self.last_fasta = FastaTable(t)
+            n, nc = int(out.n_seqs), int(out.n_calls)
+            off = np.ctypeslib.as_array(out.call_off, shape=(n + 1,)).copy()
+            calls = (np.frombuffer(C.string_at(out.calls, CALL_DTYPE.itemsize * nc), dtype=CALL_DTYPE).copy()
+                     if nc else np.zeros(0, CALL_DTYPE))
+            return tab.file_rec, tab.seq_len, tab.hdr_pos, off, calls
+        finally:
+            lib().skm_calls_free(C.byref(out))
+            lib().skm_fasta_table_free(C.byref(t))
 
     def find_best_call(self, calls: np.ndarray):
         """find_best_call (call_functions.tcc:347-659) -> (function_index, function, score, offset)."""

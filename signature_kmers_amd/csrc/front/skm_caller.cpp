@@ -112,6 +112,31 @@ int annotate_batch(skm_db* db, const std::vector<const FastaFile*>& files, const
     return rc;
 }
 
+int annotate_batch_fasta(skm_db* db, const std::vector<const FastaFile*>& files, const uint8_t* bytes,
+                         const uint64_t* file_off, const skm_annot_opts& o, skm_calls* calls, std::string& err) {
+    *calls = skm_calls{};
+    skm_fasta_table tab{};
+    int rc = skm_annotate_fasta(db, bytes, file_off, files.size(), &o, calls, &tab);
+    if (rc) {
+        err = skm_last_error();
+        return rc;
+    }
+    // the device's records against the headers-only host parse, file by file
+    for (size_t f = 0; f < files.size() && !rc; ++f) {
+        const uint64_t r0 = tab.file_rec[f], nr = tab.file_rec[f + 1] - r0;
+        bool same = nr == files[f]->size();
+        for (size_t r = 0; same && r < nr; ++r) same = tab.seq_len[r0 + r] == files[f]->len[r];
+        if (!same) {
+            err = "device FASTA parse differs from the host parse of " + files[f]->path + " (" + std::to_string(nr) +
+                  " records on the device, " + std::to_string(files[f]->size()) + " on the host, or other lengths)";
+            rc = SKM_E_STATE;
+        }
+    }
+    skm_fasta_table_free(&tab);
+    if (rc) skm_calls_free(calls);
+    return rc;
+}
+
 int best_calls_batch(const skm_calls& calls, const std::vector<const FastaFile*>& files,
                      const std::vector<const char*>& fidx, int n_threads, const std::vector<std::vector<SeqCall>*>& out,
                      std::string& err) {
@@ -157,7 +182,7 @@ int best_calls_batch(const skm_calls& calls, const std::vector<const FastaFile*>
 
 int call_files(skm_db* db, const std::vector<const FastaFile*>& files, const std::vector<std::string>& function_index,
                bool ignore_hypo, int n_threads, std::vector<std::vector<SeqCall>>& out, std::string& err,
-               double* device_ms, uint64_t max_batch_residues, double* host_ms) {
+               double* device_ms, uint64_t max_batch_residues, double* host_ms, const FastaBytes* raw) {
     const auto t_begin = std::chrono::steady_clock::now();
     double dev_ms = 0;
     skm_annot_opts o{};
@@ -171,12 +196,20 @@ int call_files(skm_db* db, const std::vector<const FastaFile*>& files, const std
         // one device batch: whole files up to max_batch_residues residues
         size_t f1 = f0;
         uint64_t nres = 0;
-        while (f1 < files.size() && (f1 == f0 || nres + files[f1]->residues.size() <= max_batch_residues))
-            nres += files[f1++]->residues.size();
+        while (f1 < files.size() && (f1 == f0 || nres + files[f1]->n_residues <= max_batch_residues))
+            nres += files[f1++]->n_residues;
         const std::vector<const FastaFile*> batch(files.begin() + f0, files.begin() + f1);
         skm_calls calls{};
         auto t0 = std::chrono::steady_clock::now();
-        int rc = annotate_batch(db, batch, o, n_threads, &calls, err);
+        int rc;
+        if (raw) {  // the batch's files as they lie in raw, their offsets from the first one's start
+            std::vector<uint64_t> off(raw->file_off.begin() + f0, raw->file_off.begin() + f1 + 1);
+            const uint64_t base = off[0];
+            for (auto& x : off) x -= base;
+            rc = annotate_batch_fasta(db, batch, raw->bytes.get() + base, off.data(), o, &calls, err);
+        } else {
+            rc = annotate_batch(db, batch, o, n_threads, &calls, err);
+        }
         dev_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (rc) return rc;
         std::vector<std::vector<SeqCall>*> outp;

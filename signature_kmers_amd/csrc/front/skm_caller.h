@@ -29,11 +29,14 @@ void set_boost_math_modes(int mean_mode, int mad_mode);
 
 // Query every sequence of every file (in order) against db.  out[f][r] is the call for record r
 // of file f.  Files are batched so one device batch holds <= max_batch_residues residues.
+// raw: the files' bytes (parse_fasta_files_bytes; files[f] is raw's file f) -- the sequence bodies
+// are then parsed on the device (annotate_batch_fasta) and the files need no residues.
 // device_ms: wall ms in skm_annotate (packing, upload, device pipeline, calls download);
 // host_ms: wall ms of the rest (batch assembly, find_best_call on n_threads host threads).
 int call_files(skm_db* db, const std::vector<const FastaFile*>& files, const std::vector<std::string>& function_index,
                bool ignore_hypo, int n_threads, std::vector<std::vector<SeqCall>>& out, std::string& err,
-               double* device_ms = nullptr, uint64_t max_batch_residues = 2000000000ull, double* host_ms = nullptr);
+               double* device_ms = nullptr, uint64_t max_batch_residues = 2000000000ull, double* host_ms = nullptr,
+               const FastaBytes* raw = nullptr);
 
 // The two halves of call_files, for callers that pipeline them (kmers-call-functions overlaps
 // parsing, the device and find_best_call over groups of files, as the reference overlaps its
@@ -46,6 +49,12 @@ bool annot_opts_for(const std::vector<std::string>& function_index, bool ignore_
 // (skm_annotate over their sequences, in file order); *calls is released with skm_calls_free
 int annotate_batch(skm_db* db, const std::vector<const FastaFile*>& files, const skm_annot_opts& o, int n_threads,
                    skm_calls* calls, std::string& err);
+// annotate_batch from the files' bytes (file f at bytes[file_off[f], file_off[f + 1]), as
+// parse_fasta_files_bytes lays them out): FastaParser's sequence bodies parsed on the device
+// (skm_annotate_fasta), no packing copy.  files are the headers-only host parses; the device's
+// record counts and lengths must equal theirs (else SKM_E_STATE, err names the file).
+int annotate_batch_fasta(skm_db* db, const std::vector<const FastaFile*>& files, const uint8_t* bytes,
+                         const uint64_t* file_off, const skm_annot_opts& o, skm_calls* calls, std::string& err);
 // the host half: find_best_call per sequence on n_threads threads; out[f] is the call vector of
 // files[f] (sized by the caller)
 int best_calls_batch(const skm_calls& calls, const std::vector<const FastaFile*>& files,

@@ -248,6 +248,55 @@ bool parse_fasta_files(const std::vector<std::string>& paths, std::vector<FastaF
     return ok;
 }
 
+bool parse_fasta_files_bytes(const std::vector<std::string>& paths, std::vector<FastaFile>& out, FastaBytes& raw,
+                             int n_threads, std::string& err) {
+    out.assign(paths.size(), FastaFile());
+    // the files' sizes give their places in the one buffer
+    raw.file_off.assign(paths.size() + 1, 0);
+    for (size_t i = 0; i < paths.size(); ++i) {
+        struct stat sb;
+        if (::stat(paths[i].c_str(), &sb) != 0) {
+            err = "cannot read " + paths[i];
+            return false;
+        }
+        raw.file_off[i + 1] = raw.file_off[i] + (uint64_t)std::max<off_t>(sb.st_size, 0);
+    }
+    raw.bytes.reset(new uint8_t[std::max<uint64_t>(raw.file_off.back(), 1)]);
+    std::atomic<size_t> next{0};
+    std::atomic<bool> ok{true};
+    std::string bad;
+    auto work = [&]() {
+        for (size_t i; (i = next.fetch_add(1)) < paths.size();) {
+            FastaFile& f = out[i];
+            f.path = paths[i];
+            f.filename = path_filename(paths[i]);
+            char* dst = reinterpret_cast<char*>(raw.bytes.get() + raw.file_off[i]);
+            const size_t n = (size_t)(raw.file_off[i + 1] - raw.file_off[i]);
+            size_t got = 0;
+            const int fd = ::open(paths[i].c_str(), O_RDONLY);
+            while (fd >= 0 && got < n) {
+                const ssize_t r = ::read(fd, dst + got, n - got);
+                if (r <= 0) break;
+                got += (size_t)r;
+            }
+            if (fd >= 0) ::close(fd);
+            if (fd < 0 || got != n) {  // the file's place in the buffer is fixed by its size
+                ok = false;
+                bad = paths[i];
+                continue;
+            }
+            parse_fasta_buffer(dst, n, f, false);
+        }
+    };
+    const int nt = std::max(1, std::min<int>(n_threads, (int)paths.size()));
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+    if (!ok) err = "cannot read " + bad;
+    return ok;
+}
+
 // ---------------------------------------------------------------------------------------------
 // paths (path_utils.h)
 // ---------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #pragma once
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <unordered_map>
@@ -44,6 +45,19 @@ void parse_fasta_buffer(const char* buf, size_t n, FastaFile& out, bool keep_res
 // (optional, one flag per path) selects the headers-only form for the files whose flag is 0.
 bool parse_fasta_files(const std::vector<std::string>& paths, std::vector<FastaFile>& out, int n_threads,
                        std::string& err, const std::vector<char>* keep_residues = nullptr);
+
+// The files of a device parse (skm_annotate_fasta): their bytes as read, back to back in one
+// buffer -- file f at [file_off[f], file_off[f + 1]) -- so that nothing is copied again before the
+// upload.
+struct FastaBytes {
+    std::unique_ptr<uint8_t[]> bytes;
+    std::vector<uint64_t> file_off;  // [n_files + 1]
+};
+// parse_fasta_files for the device parse: every file read into raw and parsed headers-only (ids,
+// definitions, lengths and the parse error reports exactly as parse_fasta_files gives them; no
+// FastaFile::residues).
+bool parse_fasta_files_bytes(const std::vector<std::string>& paths, std::vector<FastaFile>& out, FastaBytes& raw,
+                             int n_threads, std::string& err);
 
 // path_utils.h: regular files of each directory in directory_iterator (readdir) order.
 bool list_regular_files(const std::string& dir, std::vector<std::string>& out, std::string& err);

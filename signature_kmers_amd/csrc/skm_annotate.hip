@@ -32,6 +32,7 @@
 
 #include "skm_bdz.h"
 #include "skm_common.h"
+#include "skm_fasta.h"
 #include "skm_lookup.h"
 #include "skm_mphdb.h"
 #include "skm_pool.h"
@@ -1008,6 +1009,7 @@ struct skm_query {
     uint64_t n_calls = 0;
     bool ran = false;
     std::unique_ptr<HostPool> pool;  // packs the residues (created on first use)
+    std::unique_ptr<FastaWork> fasta;  // the device FASTA parser's buffers, the raw bytes among them
 };
 
 namespace {
@@ -1096,27 +1098,6 @@ void db_upload_kept(skm_db* db, const uint64_t* keys, const skm_stored_kmer_data
         SKM_CHECK(!(bad & 1u), SKM_E_ARG, "kept k-mer key 0 is not a valid k-mer");
         SKM_CHECK(!(bad & 2u), SKM_E_ARG, "duplicate kept k-mer keys");
     }
-}
-
-// hipMalloc of one of the large buffers of a DB made from a build's arena (the range-reduced table,
-// the BDZ construction's state and the BDZ DB's arrays) into an empty or smaller DevBuf; a failure
-// names the bytes asked for and the bytes free
-void alloc_reported(DevBuf& buf, uint64_t bytes, const char* what) {
-    if (buf.p && bytes <= buf.bytes) return;
-    buf.release();
-    bytes = std::max<uint64_t>(bytes, 16);
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        size_t fr = 0, tot = 0;
-        (void)hipMemGetInfo(&fr, &tot);
-        throw Error(e == hipErrorOutOfMemory ? SKM_E_OOM : SKM_E_HIP,
-                    std::string(what) + ": " + std::to_string(bytes) + " bytes asked for, " + std::to_string(fr) +
-                        " bytes free on the device (" + hipGetErrorString(e) + ")");
-    }
-    buf.p = p;
-    buf.bytes = bytes;
 }
 
 bool read_file(const char* path, std::vector<uint8_t>& out) {
@@ -1518,6 +1499,25 @@ int skm_mph_build(const uint64_t* keys, const skm_stored_kmer_data* data, size_t
 }
 
 namespace {
+// the query's stream and events, created on its first batch
+void query_stream(skm_query* q) {
+    if (q->stream) return;
+    SKM_HIP(hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking));
+    for (auto& e : q->ev) SKM_HIP(hipEventCreate(&e));
+}
+
+// the buffers query_run writes, sized for the batch now in q (nseq, n_windows; rp padded to rp_pad)
+void query_run_buffers(skm_query* q, uint64_t rp_pad) {
+    const size_t n_seqs = q->nseq;
+    q->d_hits.ensure(4 * (rp_pad + 16));
+    q->d_scr.ensure(2 * std::max<uint64_t>(q->n_windows, 1));
+    q->d_caps.ensure(4 * std::max<size_t>(n_seqs, 1));
+    q->d_cap_off.ensure(8 * (n_seqs + 1));
+    q->d_counts.ensure(4 * std::max<size_t>(n_seqs, 1));
+    q->d_call_off.ensure(8 * (n_seqs + 1));
+    q->d_seg_off.ensure(8 * (n_seqs + 1));
+}
+
 // (Re)loads a query object with a batch of sequences: the packed residues (one 0 after each
 // sequence) and the per-sequence tables on the device; the buffers only grow, so a reused query
 // (skm_annotate's, one per DB) allocates nothing once it has seen its largest batch.  Input that is
@@ -1525,10 +1525,7 @@ namespace {
 void query_setup(skm_query* q, const uint8_t* residues, const uint64_t* seq_off, const uint32_t* seq_len,
                  size_t n_seqs) {
     SKM_HIP(hipSetDevice(q->db->device));
-    if (!q->stream) {
-        SKM_HIP(hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking));
-        for (auto& e : q->ev) SKM_HIP(hipEventCreate(&e));
-    }
+    query_stream(q);
     q->ran = false;
     q->n_calls = 0;
     std::vector<QMeta> meta(n_seqs);
@@ -1588,16 +1585,29 @@ void query_setup(skm_query* q, const uint8_t* residues, const uint64_t* seq_off,
     if (packed && n_seqs)
         hipLaunchKernelGGL(k_zero_seps, dim3((uint32_t)ceil_div(n_seqs, 256)), dim3(256), 0, q->stream,
                            q->d_meta.as<QMeta>(), (uint32_t)n_seqs, q->d_res.as<uint8_t>());
-    q->d_hits.ensure(4 * (rp_pad + 16));
-    q->d_scr.ensure(2 * std::max<uint64_t>(nwin_tot, 1));
     q->d_scr_off.ensure(8 * std::max<size_t>(n_seqs, 1));
     if (n_seqs) SKM_HIP(hipMemcpyAsync(q->d_scr_off.p, scr_off.data(), 8 * n_seqs, hipMemcpyHostToDevice, q->stream));
-    q->d_caps.ensure(4 * std::max<size_t>(n_seqs, 1));
-    q->d_cap_off.ensure(8 * (n_seqs + 1));
-    q->d_counts.ensure(4 * std::max<size_t>(n_seqs, 1));
-    q->d_call_off.ensure(8 * (n_seqs + 1));
-    q->d_seg_off.ensure(8 * (n_seqs + 1));
+    query_run_buffers(q, rp_pad);
     SKM_HIP(hipStreamSynchronize(q->stream));  // the host arrays above go out of scope
+}
+
+// query_setup for raw FASTA file bytes: the device parser (skm_fasta.hip) writes the query's
+// residues, QMeta and window offsets where query_setup uploads them
+void query_setup_fasta(skm_query* q, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                       skm_fasta_table* tab) {
+    SKM_HIP(hipSetDevice(q->db->device));
+    query_stream(q);
+    q->ran = false;
+    q->n_calls = 0;
+    q->nseq = 0;
+    q->rp = q->n_windows = 0;
+    if (!q->fasta) q->fasta.reset(new FastaWork());
+    const FastaTotals t = fasta_parse(*q->fasta, bytes, file_off, n_files, q->stream, q->d_res, q->d_meta, q->d_scr_off,
+                                      0, tab);
+    q->nseq = (uint32_t)t.n_recs;
+    q->rp = t.rp;
+    q->n_windows = t.n_windows;
+    query_run_buffers(q, ceil_div(q->rp + 1, LK_POS) * LK_POS);
 }
 }  // namespace
 
@@ -1722,6 +1732,54 @@ int skm_annotate(skm_db* db, const uint8_t* residues, const uint64_t* seq_off, c
     int rc = annotate_setup(db, residues, seq_off, seq_len, n_seqs);
     if (!rc) rc = skm_query_run(db->aq, opts);
     if (!rc) rc = skm_query_calls(db->aq, out);
+    return rc;
+}
+
+int skm_query_create_fasta(skm_query** out, skm_db* db, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                           skm_fasta_table* tab) {
+    SKM_API_BEGIN
+    if (tab) std::memset(tab, 0, sizeof(*tab));
+    SKM_CHECK(out && db, SKM_E_ARG, "null argument");
+    fasta_check_args(bytes, file_off, n_files);
+    auto* q = new skm_query();
+    q->db = db;
+    try {
+        query_setup_fasta(q, bytes, file_off, n_files, tab);
+    } catch (...) {
+        skm_query_destroy(q);
+        throw;
+    }
+    *out = q;
+    SKM_API_END
+}
+
+namespace {
+int annotate_setup_fasta(skm_db* db, const uint8_t* bytes, const uint64_t* file_off, size_t n_files, skm_fasta_table* tab) {
+    SKM_API_BEGIN
+    SKM_CHECK(db, SKM_E_ARG, "null argument");
+    fasta_check_args(bytes, file_off, n_files);
+    if (!db->aq) {
+        db->aq = new skm_query();
+        db->aq->db = db;
+    }
+    query_setup_fasta(db->aq, bytes, file_off, n_files, tab);
+    SKM_API_END
+}
+}  // namespace
+
+// skm_annotate with the device parser in front: the DB's own reused query, so the raw-bytes buffer
+// and the parser's work buffers persist from batch to batch like the others
+int skm_annotate_fasta(skm_db* db, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                       const skm_annot_opts* opts, skm_calls* calls, skm_fasta_table* tab) {
+    if (tab) std::memset(tab, 0, sizeof(*tab));
+    if (!opts || !calls) {
+        set_last_error("null argument");
+        return SKM_E_ARG;
+    }
+    int rc = annotate_setup_fasta(db, bytes, file_off, n_files, tab);
+    if (!rc) rc = skm_query_run(db->aq, opts);
+    if (!rc) rc = skm_query_calls(db->aq, calls);
+    if (rc && tab) skm_fasta_table_free(tab);
     return rc;
 }
 

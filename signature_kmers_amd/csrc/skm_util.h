@@ -79,6 +79,27 @@ struct DevBuf {
     }
 };
 
+// hipMalloc of one of the large buffers (a DB made from a build's arena: the range-reduced table,
+// the BDZ construction's state and the BDZ DB's arrays; the device FASTA parser's raw bytes and
+// residues) into an empty or smaller DevBuf; a failure names the bytes asked for and the bytes free
+inline void alloc_reported(DevBuf& buf, uint64_t bytes, const char* what) {
+    if (buf.p && bytes <= buf.bytes) return;
+    buf.release();
+    if (bytes < 16) bytes = 16;
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        size_t fr = 0, tot = 0;
+        (void)hipMemGetInfo(&fr, &tot);
+        throw Error(e == hipErrorOutOfMemory ? SKM_E_OOM : SKM_E_HIP,
+                    std::string(what) + ": " + std::to_string(bytes) + " bytes asked for, " + std::to_string(fr) +
+                        " bytes free on the device (" + hipGetErrorString(e) + ")");
+    }
+    buf.p = p;
+    buf.bytes = bytes;
+}
+
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 inline int ilog2_ceil(uint64_t x) {
     int b = 0;

@@ -7,7 +7,9 @@
 // (kmers-annotate-seqs.cc:136-146,163-167).  genus-data-dir is accepted and unused, as upstream.
 // Extra options: --device N; --boost-math-stats current|legacy (the Boost.Math mean / MAD the
 // reference was compiled against, call_functions.tcc:51-53: current = >= 1.76, legacy = the older
-// single running mean and |x(mid)| MAD).
+// single running mean and |x(mid)| MAD); --fasta-parse host|device (device: the files' bytes are
+// kept, the host parses headers only and the device parses the sequence bodies in HBM,
+// skm_annotate_fasta; same output bytes and error reports).
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -39,7 +41,8 @@ int main(int argc, char** argv) {
                 {"sequences-dir", 0, false, false},   {"calls-file", 0, false, false},
                 {"uncalled-ids-file", 0, false, false}, {"parallel", 'j', false, false},
                 {"ignore-hypo", 0, true, false},      {"help", 'h', true, false},
-                {"device", 0, false, false}, {"boost-math-stats", 0, false, false}};
+                {"device", 0, false, false}, {"boost-math-stats", 0, false, false},
+                {"fasta-parse", 0, false, false}};
     op.positional = {"kmer-data-dir", "genus-data-dir", "sequences-dir", "calls-file", "uncalled-ids-file"};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
@@ -55,6 +58,7 @@ int main(int argc, char** argv) {
                   << "  --ignore-hypo                 Ignore hypothetical protein kmers when making calls\n"
                   << "  --device arg                  HIP device ordinal (default 0)\n"
                   << "  --boost-math-stats arg          current (default) | legacy Boost.Math mean/MAD\n"
+                  << "  --fasta-parse arg             host (default) | device: where the sequence bodies are parsed\n"
                   << "  -h [ --help ]                 show this help message\n\n";
         return 0;
     }
@@ -65,6 +69,9 @@ int main(int argc, char** argv) {
         if (bm != "current" && bm != "legacy") die("--boost-math-stats must be current or legacy");
         set_boost_math_modes(bm == "legacy", bm == "legacy");
     }
+    const std::string fasta_parse = op.get("fasta-parse", "host");
+    if (fasta_parse != "host" && fasta_parse != "device") die("--fasta-parse must be host or device");
+    const bool parse_on_device = fasta_parse == "device";
     const int device = std::atoi(op.get("device", "0").c_str());
     const std::string data_dir = op.get("kmer-data-dir");
     const std::string db_base = path_join(data_dir, "kmer_data");
@@ -78,11 +85,16 @@ int main(int argc, char** argv) {
     std::vector<std::string> inputs;
     if (!list_regular_files(op.get("sequences-dir"), inputs, err)) die(err);
     std::vector<FastaFile> files;
-    if (!parse_fasta_files(inputs, files, n_threads, err)) die(err);
+    FastaBytes raw;  // --fasta-parse device: the files' bytes, parsed on the device batch by batch
+    if (!(parse_on_device ? parse_fasta_files_bytes(inputs, files, raw, n_threads, err)
+                          : parse_fasta_files(inputs, files, n_threads, err)))
+        die(err);
     std::vector<const FastaFile*> fptr;
     for (auto& f : files) fptr.push_back(&f);
     std::vector<std::vector<SeqCall>> calls;
-    if (call_files(db, fptr, fidx, op.has("ignore-hypo"), n_threads, calls, err)) die(err);
+    if (call_files(db, fptr, fidx, op.has("ignore-hypo"), n_threads, calls, err, nullptr, 2000000000ull, nullptr,
+                   parse_on_device ? &raw : nullptr))
+        die(err);
     skm_db_close(db);
 
     std::ofstream anno(op.get("calls-file"));

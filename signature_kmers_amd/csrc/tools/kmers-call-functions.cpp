@@ -10,7 +10,9 @@
 // and the writer run as a pipeline over groups of files (see main).
 // Extra options: --device N; --boost-math-stats current|legacy (the Boost.Math mean / MAD the
 // reference was compiled against, call_functions.tcc:51-53: current = >= 1.76, legacy = the older
-// single running mean and |x(mid)| MAD).
+// single running mean and |x(mid)| MAD); --fasta-parse host|device (device: the parse stage keeps
+// the files' bytes and parses headers only, the device stage parses the sequence bodies in HBM,
+// skm_annotate_fasta; same output bytes and error reports).
 #include <sys/stat.h>
 
 #include <cmath>
@@ -90,7 +92,8 @@ int main(int argc, char** argv) {
     Options op;
     op.specs = {{"data-dir", 'd', false, false}, {"input-files", 'i', false, true}, {"output-files", 'o', false, false},
                 {"n-threads", 'j', false, false}, {"ignore-hypo", 0, true, false},  {"debug-hits", 0, true, false},
-                {"help", 'h', true, false},       {"device", 0, false, false}, {"boost-math-stats", 0, false, false}};
+                {"help", 'h', true, false},       {"device", 0, false, false}, {"boost-math-stats", 0, false, false},
+                {"fasta-parse", 0, false, false}};
     op.positional = {"data-dir", "input-files"};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
@@ -104,6 +107,7 @@ int main(int argc, char** argv) {
                   << "  --debug-hits                Debug kmer hits\n"
                   << "  --device arg                HIP device ordinal (default 0)\n"
                   << "  --boost-math-stats arg        current (default) | legacy Boost.Math mean/MAD\n"
+                  << "  --fasta-parse arg           host (default) | device: where the sequence bodies are parsed\n"
                   << "  -h [ --help ]               show this help message\n\n";
     };
     if (op.has("help")) {
@@ -123,6 +127,12 @@ int main(int argc, char** argv) {
         if (bm != "current" && bm != "legacy") die("--boost-math-stats must be current or legacy");
         set_boost_math_modes(bm == "legacy", bm == "legacy");
     }
+    // --fasta-parse device: the files' bytes go to the device as they are (skm_annotate_fasta); the
+    // host keeps the headers-only parse (ids, definition lines, lengths, the error reports)
+    const std::string fasta_parse = op.get("fasta-parse", "host");
+    if (fasta_parse != "host" && fasta_parse != "device") die("--fasta-parse must be host or device");
+    const bool parse_on_device = fasta_parse == "device";
+    if (parse_on_device && op.has("debug-hits")) die("--debug-hits needs the residues of --fasta-parse host");
     const int device = std::atoi(op.get("device", "0").c_str());
     // the HIP runtime initialises on a thread of its own while the DB files are read (the first
     // HIP call of a process costs ~0.1-0.3 s; skm_db_open's uploads then find it done)
@@ -168,6 +178,7 @@ int main(int argc, char** argv) {
     const size_t ng = (inputs.size() + per_group - 1) / per_group;
     struct Group {
         std::vector<FastaFile> files;
+        FastaBytes raw;  // --fasta-parse device: the files' bytes, until the device stage has taken them
         std::vector<std::vector<SeqCall>> calls;
         skm_calls dev{};
         std::string text;
@@ -202,7 +213,8 @@ int main(int argc, char** argv) {
             const std::vector<std::string> paths(inputs.begin() + g * per_group,
                                                  inputs.begin() + std::min(inputs.size(), (g + 1) * per_group));
             std::string e;
-            if (!parse_fasta_files(paths, groups[g].files, n_threads, e)) {
+            if (!(parse_on_device ? parse_fasta_files_bytes(paths, groups[g].files, groups[g].raw, n_threads, e)
+                                  : parse_fasta_files(paths, groups[g].files, n_threads, e))) {
                 for (size_t h = g; h < ng; ++h) set_state(h, -1, e);
                 return;
             }
@@ -223,10 +235,13 @@ int main(int argc, char** argv) {
             std::vector<const FastaFile*> fp;
             for (auto& f : groups[g].files) fp.push_back(&f);
             std::string e;
-            if (annotate_batch(db, fp, aopts, n_threads, &groups[g].dev, e)) {
+            Group& G = groups[g];
+            if (parse_on_device ? annotate_batch_fasta(db, fp, G.raw.bytes.get(), G.raw.file_off.data(), aopts, &G.dev, e)
+                                : annotate_batch(db, fp, aopts, n_threads, &G.dev, e)) {
                 set_state(g, -1, e);
                 continue;
             }
+            G.raw = FastaBytes();
             t_dev += secs(t);
             set_state(g, 2);
         }
