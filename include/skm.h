@@ -128,7 +128,11 @@ int skm_build_last_timings(skm_build* b, float* ms, int cap);
  * key-range pass on the group-by stream until the last stashed P^2 / variance chain is done.
  * [13], [14]: the start and end of the run's first giant-chain launch (k_heavy's chains of
  * >= 2^giant_class samples; with route_first the heavy-only pass 0's), in ms from the run's
- * start; -1 when no giant chain ran. */
+ * start; -1 when no giant chain ran.
+ * [15], [16]: the main stream's waits for a pass tail on the tail stream (one GPU with key-range
+ * passes), summed over the passes: [15] a staging's wait for the end of the tail of the pass
+ * before last, whose element buffer it overwrites (inside [2]'s span); [16] a group-by's wait for
+ * the previous tail's job sort, after which the job and big-group lists are free. */
 /* Per-kernel device time (diagnostics and the bench's roofline): with enable != 0 every kernel
  * launch of a run -- or only the launches of the kernel named `only` (e.g. "k_bucket_process";
  * NULL = all) -- is bracketed by an event pair on its stream, and after the run's host

@@ -801,7 +801,9 @@ enum : uint32_t {
     PLAN_Q_HEAVY = 5,
     PLAN_Q_REST = 6,
     PLAN_Q_LIGHT = 7,   // k_ovf_light's queue over all NOVF entries
-    PLAN_SLOTS = 8
+    PLAN_ELEMS = 8,     // the entries' elements: bounds what the pass's overflow can still keep
+    PLAN_NLOC = 9,      // the pass's elements
+    PLAN_SLOTS = 16
 };
 
 constexpr int JOB_CLASSES = 32;
@@ -4856,7 +4858,11 @@ struct PlanArgs {
     const unsigned long long* nloc;     // elements the pass groups
     unsigned long long* run;
     uint32_t* plan;
-    uint32_t ovf_cap, split_min, heavy_min;
+    // tail_async: the previous pass's plan and counters while its overflow and big groups may still
+    // append to the arena (null: everything before this pass is in the cursor)
+    const uint32_t* prev_plan;
+    const unsigned long long* prev_ctr;
+    uint32_t ovf_cap, split_min, heavy_min, big_cap;
     uint64_t kept_cap, tot_cap, split_cap;
 };
 
@@ -4946,7 +4952,24 @@ __global__ __launch_bounds__(1024) void k_ovf_plan(PlanArgs P) {
         if (raw > P.ovf_cap) atomicOr(&R[RUN_FLAGS], RUN_F_CAP);
         const bool over = tot > P.tot_cap || split > P.split_cap;
         if (over) atomicOr(&R[RUN_FLAGS], RUN_F_RERUN);
-        if (P.kept[0] + nl > P.kept_cap) atomicOr(&R[RUN_FLAGS], RUN_F_ARENA);
+        // the cursor may lack what the previous pass still appends (never an under-count, and with
+        // the cursor never more than that pass's elements, so an arena of one slot per valid window
+        // still takes every run):
+        //  - its overflow: a kept k-mer takes at least one element of the entries, and the overflow
+        //    counts its kept k-mers (ctr[8]) after it reserved their slots -- read before the cursor,
+        //    the count is never ahead of the overflow's share of the cursor;
+        //  - its group-by's big groups: one slot per descriptor at most, each of more than 64
+        //    elements outside the entries (k_ovf_light's descriptors are elements of the entries)
+        uint64_t pend = 0;
+        if (P.prev_plan) {
+            const uint64_t pe = P.prev_plan[PLAN_ELEMS], pn = P.prev_plan[PLAN_NLOC];
+            const uint64_t done = atomicAdd(const_cast<unsigned long long*>(&P.prev_ctr[8]), 0ull);
+            const uint64_t nd = atomicAdd(const_cast<unsigned long long*>(&P.prev_ctr[5]), 0ull);
+            __threadfence();
+            pend = (pe - min(pe, done)) + min(min(nd, (uint64_t)P.big_cap), (pn - min(pn, pe)) / 65);
+        }
+        const uint64_t cur = atomicAdd(const_cast<unsigned long long*>(&P.kept[0]), 0ull);
+        if (cur + pend + nl > P.kept_cap) atomicOr(&R[RUN_FLAGS], RUN_F_ARENA);
         // a pass that does not fit is skipped (the step is redone); after an error every pass is.
         // The passes after a mere overrun still run, so their demands are known for the redo
         const bool skip = over || (atomicAdd(&R[RUN_FLAGS], 0ull) & (RUN_F_ARENA | RUN_F_CAP)) != 0;
@@ -4958,6 +4981,8 @@ __global__ __launch_bounds__(1024) void k_ovf_plan(PlanArgs P) {
         P.plan[PLAN_Q_HEAVY] = 0;
         P.plan[PLAN_Q_REST] = 0;
         P.plan[PLAN_Q_LIGHT] = 0;
+        P.plan[PLAN_ELEMS] = (uint32_t)min<uint64_t>(s_elems, 0xFFFFFFFFull);
+        P.plan[PLAN_NLOC] = (uint32_t)min<uint64_t>(nl, 0xFFFFFFFFull);
         R[RUN_ACC_NOVF] += n;
         R[RUN_ACC_OVF_ELEMS] += s_elems;
         R[RUN_ACC_GROUPED] += nl;
@@ -5240,13 +5265,13 @@ struct skm_build {
     hipStream_t stream = nullptr;
     // timing events, one set per key-range pass (read after the step's single host sync)
     struct EvSet {
-        hipEvent_t ev[13] = {}, o[3] = {}, o3[3] = {};
+        hipEvent_t ev[16] = {}, o[3] = {}, o3[3] = {};
     };
     std::deque<EvSet> evsets;
     hipEvent_t* ev = nullptr;           // the current pass's set
     hipEvent_t* ev_o = nullptr;
     hipEvent_t* ev_o3 = nullptr;
-    float last_ms[15] = {};
+    float last_ms[17] = {};
     uint64_t ovf_elems = 0, ovf_kept = 0, ovf_light_sub = 0, ovf_light_elems = 0, bpk_tasks = 0, bpk_batches = 0;
 
     // host staging (reference emission order, only sequences with a kept function)
@@ -5289,7 +5314,10 @@ struct skm_build {
     // device work
     DevBuf d_hist, d_offs, d_partial, d_rbbase, d_bstart32, d_bstart, d_owner_start;
     DevBuf d_recs_hi, d_recs_lo, d_tmp_hi, d_tmp_lo;
-    DevBuf d_stg_hi, d_stg_lo;          // tail_async: the level-0 staging (else tmp holds it)
+    // tail_async: tmp and stg swap roles by pass parity (pass_hi / pass_lo): a pass stages into its
+    // buffer, the split empties it into recs, the partition scatters back into it, and the pass's
+    // group-by, overflow and tail read it there while the next pass works in the other one
+    DevBuf d_stg_hi, d_stg_lo;
     DevBuf d_part_order;                // k_part_order's workgroup -> bucket map
     DevBuf d_cur0, d_cur1, d_slices;   // staged scatter cursors
     DevBuf d_flagbits;
@@ -5328,8 +5356,10 @@ struct skm_build {
     hipStream_t stream2 = nullptr, stream3 = nullptr;
     hipStream_t stream_tail = nullptr;  // tail_async: a pass's big groups, main chains and accounting
     hipStream_t stream_tail2 = nullptr; //   the groups of 1025..CAP members beside the smaller big groups
-    hipEvent_t ev_tail_bp = nullptr, ev_tail_done = nullptr, ev_tail2 = nullptr;
-    bool tail_pending = false;          // the last pass's tail is still in flight on stream_tail
+    hipEvent_t ev_tail_bp = nullptr, ev_tail_done[2] = {}, ev_tail2 = nullptr;
+    bool tail_pending[2] = {};          // by pass parity: that pass's tail is still in flight on stream_tail
+    hipEvent_t ev_tail_jobs = nullptr;  // the tail is past k_big_append and its job sort: d_jobs, d_big_* are free
+    bool jobs_pending = false;
     uint64_t free_after_prepare = 0;    // device bytes free after prepare (counters [44])
     hipEvent_t ev_part = nullptr, ev_split = nullptr, ev_light = nullptr;
     DevBuf d_hv_keys, d_hv_rec, d_hv_len, d_hv_s0, d_hv_s1;   // heavy keys of the split overflow
@@ -5386,7 +5416,7 @@ struct skm_build {
     struct Acc {
         uint64_t novf, jobs, lens, ovf_elems, ovf_kept, big, big_kept, grouped;
     } acc{};
-    float pass_ms[12] = {};
+    float pass_ms[14] = {};
     skm::Tune tune;
     // key-range passes: the long chains leave their pass (stashed samples, run-level job list) and
     // run in batches on a fourth stream (mid-run and at the end), overlapping the later passes
@@ -5843,7 +5873,7 @@ void prepare_local(skm_build* b) {
     b->d_bstart32.ensure(sizeof(uint32_t) * (NB + 1));
     b->d_bstart.ensure(sizeof(uint64_t) * (NB + 1));
     b->d_owner_start.ensure(sizeof(uint64_t) * 80);
-    b->d_ctr.ensure(2 * 256);
+    b->d_ctr.ensure(3 * 256);
     b->d_dfunc.ensure(sizeof(uint32_t) * std::max<uint32_t>(b->opts.n_functions, 1));
     b->d_swf.ensure(sizeof(uint32_t) * std::max<uint32_t>(b->opts.n_functions, 1));
 }
@@ -6351,16 +6381,30 @@ void emit_group(skm_build* b, uint32_t g, hipStream_t st) {
     if (st != b->stream) SKM_HIP(hipEventRecord(b->ev_emit, st));
 }
 
-// d_ctr: [0] the kept arena cursor, [2] the flag count (run-level); the pass counters at 32
-inline unsigned long long* pass_ctr(skm_build* b) { return b->d_ctr.as<unsigned long long>() + 32; }
+// d_ctr: [0] the kept arena cursor, [2] the flag count (run-level); the pass counters at 32, and
+// (tail_async) the odd passes' at 64: a pass's side streams and tail still count in its block while
+// the next pass clears and fills the other
+inline uint32_t pass_par(const skm_build* b, uint32_t pass) { return tail_async_on(b) ? pass & 1u : 0u; }
+inline unsigned long long* pass_ctr(skm_build* b, uint32_t pass) {
+    return b->d_ctr.as<unsigned long long>() + 32 + 32 * pass_par(b, pass);
+}
+// the pass's element buffer beside recs (tail_async: tmp and stg by parity; else tmp)
+inline uint64_t* pass_hi(skm_build* b, uint32_t pass) { return (pass_par(b, pass) ? b->d_stg_hi : b->d_tmp_hi).as<uint64_t>(); }
+inline uint64_t* pass_lo(skm_build* b, uint32_t pass) { return (pass_par(b, pass) ? b->d_stg_lo : b->d_tmp_lo).as<uint64_t>(); }
 
-// the main stream waits for the previous pass's tail (tail_async) before it overwrites what the tail
-// reads (the partition's tmp, the counters, the job lists; not recs: k_partition is its last reader)
-// or reads what it writes (the stash cursors, the kept arena's totals)
+// tail_async: the main stream waits for the tail of the pass before last, which read the element
+// buffer and the counter block that this pass's staging and partition are about to overwrite.  The
+// previous pass's tail works in the other buffer and block and is not waited for.
+void join_tail_par(skm_build* b, uint32_t par) {
+    if (!b->tail_pending[par]) return;
+    SKM_HIP(hipStreamWaitEvent(b->stream, b->ev_tail_done[par], 0));
+    b->tail_pending[par] = false;
+}
+// every tail in flight: before the main stream reads what a tail writes (the stash cursors, the kept
+// arena's totals)
 void join_tail(skm_build* b) {
-    if (!b->tail_pending) return;
-    SKM_HIP(hipStreamWaitEvent(b->stream, b->ev_tail_done, 0));
-    b->tail_pending = false;
+    join_tail_par(b, 0);
+    join_tail_par(b, 1);
 }
 
 void phase_extract(skm_build* b, uint32_t pass) {
@@ -6436,12 +6480,14 @@ void phase_extract(skm_build* b, uint32_t pass) {
         SKM_LAUNCH(b, k_stage_init, dim3((NB + 255) / 256), dim3(256), 0, st, bstart, NB, nbits - SC_L0_BITS, cur0, cur1,
                    slices);
     }
-    // the level-0 staging: tmp, or (tail_async) a buffer of its own, so it overlaps the previous
-    // pass's tail, which still reads tmp and recs
-    const bool sep = tail_async_on(b);
-    uint64_t* stg_hi = (sep ? b->d_stg_hi : b->d_tmp_hi).as<uint64_t>();
-    uint64_t* stg_lo = (sep ? b->d_stg_lo : b->d_tmp_lo).as<uint64_t>();
-    if (!sep) join_tail(b);
+    // the level-0 staging, into the pass's element buffer: (tail_async) the first write to it since
+    // the pass before last, whose tail is waited for here (timings [15]); the previous pass's tail
+    // runs on beside the staging, the split and the partition
+    uint64_t* stg_hi = pass_hi(b, pass);
+    uint64_t* stg_lo = pass_lo(b, pass);
+    SKM_HIP(hipEventRecord(b->ev[13], st));
+    join_tail_par(b, pass_par(b, pass));
+    SKM_HIP(hipEventRecord(b->ev[14], st));
     if (b->pass_bits && b->tune.stage_round == 1)
         SKM_LAUNCH_AS(b, "k_extract_stage_pos", (k_extract_stage_pos<SC_ROUND_HALF, 4>), dim3(nwg), dim3(EX_THREADS), 0, st, X,
                    b->d_posg.as<uint64_t>() + (uint64_t)(pass % b->emit_g) * std::max<uint64_t>(b->pass_max, 1),
@@ -6456,8 +6502,8 @@ void phase_extract(skm_build* b, uint32_t pass) {
                    cur0, stg_hi, stg_lo);
     else
         SKM_LAUNCH(b, k_extract_stage, dim3(nwg), dim3(EX_THREADS), 0, st, X, cur0, stg_hi, stg_lo);
-    // (the split overwrites recs, which only k_partition reads: the previous pass's tail reads tmp and
-    // is joined before the partition, in phase_group)
+    // (the split overwrites recs, which only k_partition reads: the previous pass's tail reads its
+    // own element buffer)
     const uint32_t nsl = (uint32_t)(ceil_div(b->pass_max, SC_SLICE) + (1u << SC_L0_BITS));
     SKM_LAUNCH(b, k_split_stage, dim3(nsl), dim3(EX_THREADS), 0, st, stg_hi,
                        stg_lo, bstart, nbits, slices, cur1, b->d_recs_hi.as<uint64_t>(), b->d_recs_lo.as<uint64_t>());
@@ -6623,7 +6669,7 @@ void launch_chains(skm_build* b, hipStream_t st, const Job* jobs, const unsigned
                        long_class);
     SKM_LAUNCH(b, k_job_scatter, dim3(JOB_NWG), dim3(JOB_WG), 0, st, jobs, nj_d, cap, cs.offs.as<uint64_t>(),
                        cs.sorted.as<Job>());
-    if (st_short && ev_sorted) SKM_HIP(hipEventRecord(ev_sorted, st));  // sorted jobs ready
+    if (ev_sorted) SKM_HIP(hipEventRecord(ev_sorted, st));  // sorted jobs ready (the list itself is free)
     // k_job_scan leaves the long jobs' count after the offsets; they lead the sorted order
     const uint64_t* nlong_d = cs.offs.as<uint64_t>() + (uint64_t)JOB_NWG * JOB_CLASSES;
     const auto* nlong_u = reinterpret_cast<const unsigned long long*>(nlong_d);
@@ -6665,22 +6711,21 @@ void phase_group(skm_build* b, uint32_t pass) {
     hipStream_t st = b->stream, st2 = b->stream2, st3 = b->stream3;
     const bool multi = b->world > 1;
     const uint32_t NB1 = 1u << b->b1_bits;
-    // the previous pass's tail still reads tmp, the counters and the job lists, all written from
-    // here on; the staging and the split before this point ran beside it
-    join_tail(b);
     SKM_HIP(hipEventRecord(b->ev[4], st));
     // per-pass counters; [0] (kept k-mers: the arena cursor) and the signature flags run over
-    // all passes (begin_run clears them)
-    unsigned long long* ctr_d = pass_ctr(b);
+    // all passes (begin_run clears them).  tail_async: the counters, the plan and the sorted overflow
+    // list are the pass parity's copies -- the previous pass's overflow streams and tail still use theirs
+    const uint32_t par = pass_par(b, pass);
+    unsigned long long* ctr_d = pass_ctr(b, pass);
     SKM_HIP(hipMemsetAsync(ctr_d, 0, 256, st));
     unsigned long long* run_d = b->d_run.as<unsigned long long>();
-    uint32_t* plan_d = b->d_plan.as<uint32_t>();
-    OvfEntry* ovf2_d = b->d_ovf2.as<OvfEntry>();
+    uint32_t* plan_d = b->d_plan.as<uint32_t>() + par * PLAN_SLOTS;
+    OvfEntry* ovf2_d = b->d_ovf2.as<OvfEntry>() + (uint64_t)par * std::max<uint64_t>(b->ovf_cap, 1);
     BucketArgs A;
     A.recs_hi = (multi ? b->d_rhi : b->d_recs_hi).as<uint64_t>();
     A.recs_lo = (multi ? b->d_rlo : b->d_recs_lo).as<uint64_t>();
-    A.tmp_hi = b->d_tmp_hi.as<uint64_t>();
-    A.tmp_lo = b->d_tmp_lo.as<uint64_t>();
+    A.tmp_hi = pass_hi(b, pass);
+    A.tmp_lo = pass_lo(b, pass);
     const uint32_t pc = pass_copy(b, pass);  // world 1: NB1 buckets in the pass's copies
     A.bstart = multi ? b->d_vstart.as<uint64_t>() : b->d_bstart.as<uint64_t>() + (uint64_t)pc * (NB1 + 1);
     A.seg_start = multi ? b->d_seg_start.as<uint64_t>() : nullptr;
@@ -6744,6 +6789,11 @@ void phase_group(skm_build* b, uint32_t pass) {
     P.nloc = nloc_d;
     P.run = run_d;
     P.plan = plan_d;
+    // the previous pass's overflow and big groups may not have appended yet (no join before this point)
+    const bool prev = tail_async_on(b) && pass > 0;
+    P.prev_plan = prev ? b->d_plan.as<uint32_t>() + (par ^ 1u) * PLAN_SLOTS : nullptr;
+    P.prev_ctr = prev ? pass_ctr(b, pass - 1) : nullptr;
+    P.big_cap = A.big_cap;
     P.ovf_cap = (uint32_t)b->ovf_cap;
     P.split_min = split_min;
     P.heavy_min = (uint32_t)b->tune.ovf_heavy;
@@ -6813,6 +6863,15 @@ void phase_group(skm_build* b, uint32_t pass) {
     SKM_HIP(hipEventRecord(b->ev_part, st));
     SKM_HIP(hipStreamWaitEvent(st2, b->ev_part, 0));
     SKM_HIP(hipStreamWaitEvent(st3, b->ev_part, 0));
+    // the previous pass's per-lane overflow chains (stream 3) read the chain lengths that stream 2
+    // writes from here on (the tail's join used to order them)
+    if (prev) SKM_HIP(hipStreamWaitEvent(st2, b->evsets[pass - 1].o3[1], 0));
+    // k_ovf_light and k_overflow append big-group descriptors, which the previous tail's
+    // k_big_groups / k_big_append still read (the main stream's own wait is before the group-by)
+    if (b->jobs_pending) {
+        SKM_HIP(hipStreamWaitEvent(st2, b->ev_tail_jobs, 0));
+        SKM_HIP(hipStreamWaitEvent(st3, b->ev_tail_jobs, 0));
+    }
     SKM_HIP(hipEventRecord(b->ev_o[0], st2));
     SKM_HIP(hipEventRecord(b->ev_o3[0], st3));
     if (H.giant_min) SKM_HIP(hipMemsetAsync(b->gcount[pass].p, 0, 16, st2));
@@ -6862,6 +6921,14 @@ void phase_group(skm_build* b, uint32_t pass) {
     BA.tmp_lo = A.tmp_lo;
     BA.flags = A.flags;
     BA.out = b->d_big_out.as<BigOut>();
+    // tail_async: the group-by refills the job list, the big-group descriptors and their outputs, which
+    // the previous pass's tail reads up to its job sort (timings [16]: by the timeline it is there
+    // long before the staging, the split and the partition of this pass are done)
+    SKM_HIP(hipEventRecord(b->ev[15], st));
+    if (b->jobs_pending) {
+        SKM_HIP(hipStreamWaitEvent(st, b->ev_tail_jobs, 0));
+        b->jobs_pending = false;
+    }
     SKM_HIP(hipEventRecord(b->ev[11], st));
     // persistent: two workgroups per CU take the pass's (bucket, part) tasks from ctr_d[CTR_BPK_TASK]
     SKM_LAUNCH(b, k_bucket_process, dim3(std::min<uint32_t>(NB1 * BPK_PARTS, 2u * b->n_cus)), dim3(BPK_THREADS), 0, st, A);
@@ -6876,7 +6943,8 @@ void phase_group(skm_build* b, uint32_t pass) {
         b->emit_q = (pass + 1) / b->emit_g;
     }
     // the pass's tail: on the main stream, or (tail_async) on its own stream beside the next pass's
-    // staging and split -- the next partition waits for it (join_tail)
+    // staging, split and partition -- the next group-by waits for its job sort, the staging of the
+    // pass after next for its end (join_tail_par)
     const bool tail_async = tail_async_on(b);
     hipStream_t tt = tail_async ? b->stream_tail : st;
     if (tail_async) {
@@ -6914,7 +6982,9 @@ void phase_group(skm_build* b, uint32_t pass) {
     SKM_HIP(hipGetLastError());
     SKM_HIP(hipEventRecord(b->ev[12], tt));
     launch_chains(b, tt, A.jobs, ctr_d + 3, b->jobs_cap, b->cs_main, A.lens, reinterpret_cast<const uint32_t*>(A.recs_hi),
-                  reinterpret_cast<const uint32_t*>(A.tmp_hi), nullptr, A.out_data, (uint32_t)b->tune.main_long_class);
+                  reinterpret_cast<const uint32_t*>(A.tmp_hi), nullptr, A.out_data, (uint32_t)b->tune.main_long_class,
+                  nullptr, tail_async ? b->ev_tail_jobs : nullptr);
+    b->jobs_pending = tail_async;
     SKM_HIP(hipStreamWaitEvent(tt, b->ev_o[2], 0));
     SKM_HIP(hipStreamWaitEvent(tt, b->ev_o3[1], 0));
     SKM_HIP(hipEventRecord(b->ev[6], tt));
@@ -6924,8 +6994,8 @@ void phase_group(skm_build* b, uint32_t pass) {
     SKM_HIP(hipGetLastError());
     SKM_HIP(hipEventRecord(b->ev[7], tt));
     if (tail_async) {
-        SKM_HIP(hipEventRecord(b->ev_tail_done, tt));
-        b->tail_pending = true;
+        SKM_HIP(hipEventRecord(b->ev_tail_done[par], tt));
+        b->tail_pending[par] = true;
     }
 }
 
@@ -6948,8 +7018,8 @@ void alloc_caps(skm_build* b) {
     b->d_hv_len.ensure(4 * Sp);
     b->d_hv_s0.ensure(4 * Sp);
     b->d_hv_s1.ensure(4 * Sp);
-    b->d_ovf2.ensure(sizeof(OvfEntry) * std::max<uint64_t>(b->ovf_cap, 1));
-    b->d_plan.ensure(4 * PLAN_SLOTS);
+    b->d_ovf2.ensure(2 * sizeof(OvfEntry) * std::max<uint64_t>(b->ovf_cap, 1));  // by pass parity (tail_async)
+    b->d_plan.ensure(2 * 4 * PLAN_SLOTS);
     b->d_run.ensure(8 * RUN_SLOTS);
     b->d_sub_tab.ensure(4ull * (1u << b->b1_bits) * SUB_TAB);
     b->d_stamps.ensure(32 * 8);
@@ -6993,9 +7063,9 @@ void begin_run(skm_build* b) {
     alloc_caps(b);
     b->emit_q = -1;  // no pass group's positions are queued from an earlier (possibly aborted) run
     b->giant_timed = false;
-    b->tail_pending = false;
+    b->tail_pending[0] = b->tail_pending[1] = b->jobs_pending = false;
     SKM_HIP(hipEventRecord(b->ev_start, st));
-    SKM_HIP(hipMemsetAsync(b->d_ctr.p, 0, 2 * 256, st));
+    SKM_HIP(hipMemsetAsync(b->d_ctr.p, 0, 3 * 256, st));
     SKM_HIP(hipMemsetAsync(b->d_run.p, 0, 8 * RUN_SLOTS, st));
     SKM_HIP(hipMemsetAsync(b->d_flags.p, 0, b->n_total ? b->n_total : 1, st));
     SKM_HIP(hipMemsetAsync(b->d_flagbits.p, 0, 4 * ((b->n_total + 31) / 32 + 1), st));
@@ -7043,12 +7113,14 @@ void use_evset(skm_build* b, uint32_t pass) {
 // after the step's sync: phase times of every pass
 void pass_times(skm_build* b, uint32_t npass) {
     // [0] extract-count [1] scan [2] extract-scatter [3] bucket [5] chains [8] exchange
-    // [9] partition [10] group-by kernel [11] big groups; [4] overflow (own streams)
-    const int idx[9] = {0, 1, 2, 3, 5, 8, 9, 10, 11};
-    const int from[9] = {0, 1, 2, 4, 12, 3, 4, 11, 5}, to[9] = {1, 2, 3, 12, 6, 4, 10, 5, 12};
+    // [9] partition [10] group-by kernel [11] big groups; [4] overflow (own streams); [12] the
+    // staging's wait for the tail of the pass before last (inside [2]'s span) [13] the group-by's
+    // wait for the previous tail's job sort
+    const int idx[11] = {0, 1, 2, 3, 5, 8, 9, 10, 11, 12, 13};
+    const int from[11] = {0, 1, 2, 4, 12, 3, 4, 11, 5, 13, 15}, to[11] = {1, 2, 3, 12, 6, 4, 10, 5, 12, 14, 11};
     for (uint32_t p = 0; p < npass && p < b->evsets.size(); ++p) {
         const skm_build::EvSet& e = b->evsets[p];
-        for (int i = 0; i < 9; ++i) {
+        for (int i = 0; i < 11; ++i) {
             float t = 0.f;
             SKM_HIP(hipEventElapsedTime(&t, e.ev[from[i]], e.ev[to[i]]));
             b->pass_ms[idx[i]] += t;
@@ -7184,6 +7256,8 @@ void phase_final(skm_build* b) {
     SKM_HIP(hipEventElapsedTime(&b->last_ms[6], b->ev[7], b->ev[8]));      // stats (+ reductions)
     SKM_HIP(hipEventElapsedTime(&b->last_ms[7], b->ev_start, b->ev[8]));   // whole run
     SKM_HIP(hipEventElapsedTime(&b->last_ms[12], b->ev_tail[0], b->ev_tail[1]));  // long-chain tail
+    b->last_ms[15] = b->pass_ms[12];  // the main stream's waits for a tail's end, and
+    b->last_ms[16] = b->pass_ms[13];  //   for a tail's job sort
     b->last_ms[13] = b->last_ms[14] = -1.0f;  // the first giant chains' start / end from the run's start
     if (b->giant_timed) {
         SKM_HIP(hipEventElapsedTime(&b->last_ms[13], b->ev_start, b->ev_giant[0]));
@@ -7328,7 +7402,8 @@ int skm_build_create(skm_build** out, const int* devices, int n_devices, const s
     SKM_HIP(hipStreamCreateWithFlags(&b->stream_tail2, hipStreamNonBlocking));
     SKM_HIP(hipEventCreateWithFlags(&b->ev_tail2, hipEventDisableTiming));
     SKM_HIP(hipEventCreateWithFlags(&b->ev_tail_bp, hipEventDisableTiming));
-    SKM_HIP(hipEventCreateWithFlags(&b->ev_tail_done, hipEventDisableTiming));
+    for (auto& e : b->ev_tail_done) SKM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    SKM_HIP(hipEventCreateWithFlags(&b->ev_tail_jobs, hipEventDisableTiming));
     use_evset(b, 0);
     SKM_HIP(hipEventCreate(&b->ev_start));
     SKM_HIP(hipStreamCreateWithFlags(&b->chain_st, hipStreamNonBlocking));
@@ -7912,7 +7987,7 @@ int skm_build_kernel_timings(skm_build* b, char* names, size_t names_cap, float*
 
 int skm_build_last_timings(skm_build* b, float* ms, int cap) {
     if (!b || !ms) return SKM_E_ARG;
-    int n = std::min(cap, 15);
+    int n = std::min(cap, 17);
     for (int i = 0; i < n; ++i) ms[i] = b->last_ms[i];
     return n;
 }
@@ -8260,7 +8335,9 @@ void skm_build_destroy(skm_build* b) {
     if (b->stream_tail2) (void)hipStreamDestroy(b->stream_tail2);
     if (b->ev_tail2) (void)hipEventDestroy(b->ev_tail2);
     if (b->ev_tail_bp) (void)hipEventDestroy(b->ev_tail_bp);
-    if (b->ev_tail_done) (void)hipEventDestroy(b->ev_tail_done);
+    for (auto& e : b->ev_tail_done)
+        if (e) (void)hipEventDestroy(e);
+    if (b->ev_tail_jobs) (void)hipEventDestroy(b->ev_tail_jobs);
     delete b;
 }
 
