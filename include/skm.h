@@ -462,7 +462,8 @@ int skm_mph_db_plan(uint64_t n, uint64_t out[4]);
 /* ------------------------------------------------------------------------------------------
  * Function calling.  Replaces FunctionCaller<CmphKmerDb>::process_aa_seq for a batch of query
  * sequences (call_functions.tcc:259-338 + HitSet :6-108, window iterator kmer_data.h:76-102).
- * find_best_call (call_functions.tcc:347-659) stays on the host: skm_find_best_call.
+ * find_best_call (call_functions.tcc:347-659): skm_find_best_call for one sequence on the host;
+ * for a batch, on the host or on the resident calls, the "Best call per sequence" section below.
  * ------------------------------------------------------------------------------------------ */
 typedef struct skm_annot_opts {
     int32_t min_hits;      /* 5   (call_functions.h:66)                                   */
@@ -646,6 +647,62 @@ void skm_matrix_batch_destroy(skm_matrix_batch* b);
 int skm_find_best_call(const skm_kmer_call* calls, size_t ncalls, const char* const* function_index,
                        size_t nfunc, uint16_t* out_fi, float* out_score, float* out_offset,
                        char* out_func, size_t out_func_cap);
+
+/* ------------------------------------------------------------------------------------------
+ * Best call per sequence for a whole batch, on the host or on the device.  The same decision as
+ * skm_find_best_call (call_functions.tcc:347-659) made on ids: the strings of function.index are
+ * reduced once to tables (skm_fidx: the rank of every name under std::string order, and string-pool
+ * ids of the name and of its split(" / ") parts), and one core (csrc/skm_bestcall.h) runs per
+ * sequence in a device kernel and in the host batch function alike.
+ *
+ * The core declines ("defers") a sequence only when it has more than SKM_BEST_MAX_CALLS calls or
+ * one of its calls names a function of more than SKM_BEST_MAX_PARTS parts; the library resolves
+ * those with skm_find_best_call from that sequence's calls and reports how many there were.
+ * ------------------------------------------------------------------------------------------ */
+#define SKM_BEST_MAX_PARTS 8
+#define SKM_BEST_MAX_CALLS 64
+#define SKM_BEST_PAIR 1
+
+typedef struct skm_fidx skm_fidx;
+/* device >= 0: the tables are uploaded there too; device < 0: host only (no HIP call is made).
+ * A NULL entry of function_index is the name "". */
+int skm_fidx_create(skm_fidx** out, const char* const* function_index, size_t nfunc, int device);
+void skm_fidx_destroy(skm_fidx* fx);
+
+typedef struct skm_best_call {       /* 16 bytes */
+    uint16_t fi;        /* out_fi of skm_find_best_call                                          */
+    uint16_t fi_a, fi_b;/* SKM_BEST_PAIR: the "f1 ?? f2" functions, f1 = fi_a (the greater name); */
+                        /* else SKM_UNDEFINED_FUNCTION                                           */
+    uint16_t flags;     /* SKM_BEST_PAIR = 1                                                     */
+    float score, offset;
+} skm_best_call;
+typedef struct skm_best_calls {      /* library-owned; skm_best_calls_free */
+    skm_best_call* best;  /* [n_seqs] */
+    uint64_t n_seqs, n_calls, n_windows, n_deferred;
+    float kernel_ms;      /* device time of the best-call kernel (0 on the host)                 */
+} skm_best_calls;
+/* The function string find_best_call returns: name(fi), "f1 ?? f2", or "".  Returns the length
+ * of the whole string (truncated to cap - 1 bytes in out), or < 0 on error. */
+int skm_best_call_name(const skm_fidx* fx, const skm_best_call* c, char* out, size_t cap);
+
+/* host batch (no device): the same core on n_threads host threads; works on a CPU-only machine.
+ * Only call_off, calls and the counts of `calls` are read. */
+int skm_best_calls_host(const skm_calls* calls, const skm_fidx* fx, int n_threads, skm_best_calls* out);
+/* On the resident calls of q's last run: kernel on q's stream, 16 B per sequence downloaded; the
+ * calls themselves are not downloaded unless a sequence was deferred.  SKM_E_ARG: fx without
+ * device tables or made for another device than q's; SKM_E_STATE: q has not run. */
+int skm_query_best_calls(skm_query* q, const skm_fidx* fx, skm_best_calls* out);
+/* skm_annotate / skm_annotate_fasta + the above, through the DB's kept query */
+int skm_annotate_best(skm_db* db, const uint8_t* residues, const uint64_t* seq_off, const uint32_t* seq_len,
+                      size_t n_seqs, const skm_annot_opts* opts, const skm_fidx* fx, skm_best_calls* out);
+int skm_annotate_fasta_best(skm_db* db, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                            const skm_annot_opts* opts, const skm_fidx* fx, skm_best_calls* out,
+                            skm_fasta_table* tab);
+/* Test vehicle: a caller-made CSR of calls through the kernel on `device`, no DB and no fallback;
+ * deferred[s] = 1 where the kernel declined (their best[] entries are then unspecified). */
+int skm_debug_best_calls(const skm_kmer_call* calls, const uint64_t* call_off, size_t n_seqs,
+                         const skm_fidx* fx, int device, skm_best_call* best, uint8_t* deferred, float* ms);
+void skm_best_calls_free(skm_best_calls* c);
 
 #ifdef __cplusplus
 }

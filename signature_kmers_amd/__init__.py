@@ -31,6 +31,12 @@ STORED_DTYPE = np.dtype([("avg_from_end", "<u2"), ("function_index", "<u2"), ("m
 CALL_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("count", "<i4"), ("function_index", "<u2"),
                        ("pad", "<u2"), ("protein_length_median", "<u4"),
                        ("protein_length_med_avg_dev", "<f4")])  # KmerCall, call_functions.h:23-48
+# skm_best_call: find_best_call's result for one sequence; flags & BEST_PAIR: "name(fi_a) ?? name(fi_b)"
+BEST_DTYPE = np.dtype([("fi", "<u2"), ("fi_a", "<u2"), ("fi_b", "<u2"), ("flags", "<u2"), ("score", "<f4"),
+                       ("offset", "<f4")])
+BEST_PAIR = 1
+BEST_MAX_PARTS = 8
+BEST_MAX_CALLS = 64
 
 
 class SkmError(RuntimeError):
@@ -67,6 +73,11 @@ class _AnnotOpts(C.Structure):
 class _Calls(C.Structure):
     _fields_ = [("call_off", C.POINTER(C.c_uint64)), ("calls", C.c_void_p), ("n_seqs", C.c_uint64),
                 ("n_calls", C.c_uint64), ("n_windows", C.c_uint64)]
+
+
+class _BestCalls(C.Structure):
+    _fields_ = [("best", C.c_void_p), ("n_seqs", C.c_uint64), ("n_calls", C.c_uint64), ("n_windows", C.c_uint64),
+                ("n_deferred", C.c_uint64), ("kernel_ms", C.c_float)]
 
 
 class _FastaTable(C.Structure):
@@ -182,6 +193,16 @@ _SIGS = {
     "skm_matrix_tile_rows": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "skm_find_best_call": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_uint16),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_char_p, C.c_size_t]),
+    "skm_fidx_create": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_char_p), C.c_size_t, C.c_int]),
+    "skm_fidx_destroy": (None, [_P]),
+    "skm_best_call_name": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t]),
+    "skm_best_calls_host": (C.c_int, [C.POINTER(_Calls), _P, C.c_int, C.POINTER(_BestCalls)]),
+    "skm_query_best_calls": (C.c_int, [_P, _P, C.POINTER(_BestCalls)]),
+    "skm_annotate_best": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(_AnnotOpts), _P, C.POINTER(_BestCalls)]),
+    "skm_annotate_fasta_best": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(_AnnotOpts), _P, C.POINTER(_BestCalls),
+                                          C.POINTER(_FastaTable)]),
+    "skm_debug_best_calls": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, _P, _P, C.POINTER(C.c_float)]),
+    "skm_best_calls_free": (None, [C.POINTER(_BestCalls)]),
 }
 
 _lib = None
@@ -818,6 +839,99 @@ def fasta_parse_device(blobs, device: int = 0, want_residues: bool = False) -> F
         lib().skm_fasta_table_free(C.byref(t))
 
 
+class FunctionIndexTables:
+    """skm_fidx: function.index reduced to the ids find_best_call needs (name ranks, part ids), on
+    the host and -- device >= 0 -- on that device; device < 0 makes no HIP call."""
+
+    def __init__(self, function_index, device: int = 0):
+        self.function_index = list(function_index)
+        self.device = device
+        self._h = C.c_void_p()
+        arr = _fi_array(self.function_index)
+        _check(lib().skm_fidx_create(C.byref(self._h), arr, len(self.function_index), device))
+
+    def name(self, best) -> str:
+        """skm_best_call_name of one BEST_DTYPE element."""
+        return self.names(np.array(best, dtype=BEST_DTYPE).reshape(1))[0]
+
+    def names(self, best: np.ndarray) -> list:
+        """skm_best_call_name of every element: name(fi), "f1 ?? f2" or ""."""
+        best = np.ascontiguousarray(best, dtype=BEST_DTYPE)
+        fn, h, base = lib().skm_best_call_name, self._h, best.ctypes.data
+        cap = 4096
+        buf = C.create_string_buffer(cap)
+        out = []
+        for k in range(len(best)):
+            n = fn(h, base + 16 * k, buf, cap)
+            if n < 0:
+                _check(n)
+            if n >= cap:
+                cap = n + 1
+                buf = C.create_string_buffer(cap)
+                fn(h, base + 16 * k, buf, cap)
+            out.append(buf.value.decode("latin-1"))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().skm_fidx_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BestCalls:
+    """skm_best_calls: .best (BEST_DTYPE [n_seqs]), the counts, the kernel's device ms, and
+    names() through the tables that made it."""
+
+    def __init__(self, out: "_BestCalls", tables: FunctionIndexTables):
+        n = int(out.n_seqs)
+        self.best = (np.frombuffer(C.string_at(out.best, BEST_DTYPE.itemsize * n), dtype=BEST_DTYPE).copy()
+                     if n else np.zeros(0, BEST_DTYPE))
+        self.n_seqs, self.n_calls, self.n_windows = n, int(out.n_calls), int(out.n_windows)
+        self.n_deferred = int(out.n_deferred)
+        self.kernel_ms = float(out.kernel_ms)
+        self.tables = tables
+
+    def names(self) -> list:
+        return self.tables.names(self.best)
+
+
+def _best_result(out, tables):
+    try:
+        return BestCalls(out, tables)
+    finally:
+        lib().skm_best_calls_free(C.byref(out))
+
+
+def best_calls_host(call_off, calls, tables: FunctionIndexTables, n_threads: int = 16) -> BestCalls:
+    """skm_best_calls_host: find_best_call for every sequence of a CSR of calls, on host threads."""
+    call_off = np.ascontiguousarray(call_off, dtype=np.uint64)
+    calls = np.ascontiguousarray(calls, dtype=CALL_DTYPE)
+    c = _Calls(call_off.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(calls) if len(calls) else None,
+               len(call_off) - 1, len(calls), 0)
+    out = _BestCalls()
+    _check(lib().skm_best_calls_host(C.byref(c), tables._h, n_threads, C.byref(out)))
+    return _best_result(out, tables)
+
+
+def debug_best_calls(call_off, calls, tables: FunctionIndexTables, device: int = 0):
+    """skm_debug_best_calls: a CSR of calls through the kernel alone -> (best, deferred u8, ms)."""
+    call_off = np.ascontiguousarray(call_off, dtype=np.uint64)
+    calls = np.ascontiguousarray(calls, dtype=CALL_DTYPE)
+    n = len(call_off) - 1
+    best = np.zeros(n, BEST_DTYPE)
+    deferred = np.zeros(n, np.uint8)
+    ms = C.c_float()
+    _check(lib().skm_debug_best_calls(_ptr(calls) if len(calls) else None, _ptr(call_off), n, tables._h, device,
+                                      _ptr(best) if n else None, _ptr(deferred) if n else None, C.byref(ms)))
+    return best, deferred, ms.value
+
+
 class QueryBatch:
     """A batch of query sequences resident in HBM (skm_query_*): run() repeats the device pipeline
     (window lookup + HitSet calls) without re-uploading; timings() = the last run's device ms."""
@@ -870,6 +984,12 @@ class QueryBatch:
         finally:
             lib().skm_calls_free(C.byref(out))
 
+    def best_calls(self, tables: "FunctionIndexTables") -> "BestCalls":
+        """skm_query_best_calls: find_best_call on the resident calls of the last run."""
+        out = _BestCalls()
+        _check(lib().skm_query_best_calls(self._h, tables._h, C.byref(out)))
+        return _best_result(out, tables)
+
     def window_hits(self):
         """skm_query_window_hits: (hit_off [n+1], pos, fm) of the last run -- every window the
         device lookup found in the DB, as (offset in its sequence, function_index << 16 | mean)."""
@@ -896,7 +1016,8 @@ class QueryBatch:
 
 class FunctionCaller:
     """FunctionCaller<CmphKmerDb> (call_functions.h:60-136) with the per-window lookup and HitSet
-    state machine on the GPU and find_best_call on the host."""
+    state machine on the GPU and find_best_call on the host (find_best_call, per sequence) or on
+    the resident calls of the whole batch (best_seqs / best_fasta)."""
 
     def __init__(self, db: CmphKmerDb, function_index, min_hits: int = 5, max_gap: int = 200,
                  mean_mode: int = 0, mad_mode: int = 0):
@@ -967,6 +1088,42 @@ class FunctionCaller:
         finally:
             lib().skm_calls_free(C.byref(out))
             lib().skm_fasta_table_free(C.byref(t))
+
+    def tables(self) -> "FunctionIndexTables":
+        """The function-index tables on the DB's device, made on first use and kept."""
+        if getattr(self, "_tables", None) is None:
+            self._tables = FunctionIndexTables(self.function_index, self.db.device)
+        return self._tables
+
+    def best_seqs(self, residues, seq_off, seq_len) -> "BestCalls":
+        """process_aa_seq + find_best_call for a batch, both on the device (skm_annotate_best)."""
+        if self.hypo_index < 0:  # call_functions.tcc:269-274 exits the process
+            raise SkmError("Cannot find hypothetical protein index")
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        out = _BestCalls()
+        opts = self._opts()
+        _check(lib().skm_annotate_best(self.db._h, _ptr(residues), _ptr(seq_off), _ptr(seq_len), len(seq_len),
+                                       C.byref(opts), self.tables()._h, C.byref(out)))
+        return _best_result(out, self.tables())
+
+    def best_fasta(self, blobs) -> "BestCalls":
+        """process_fasta + find_best_call from the files' bytes (skm_annotate_fasta_best);
+        self.last_fasta is the FastaTable."""
+        if self.hypo_index < 0:  # call_functions.tcc:269-274 exits the process
+            raise SkmError("Cannot find hypothetical protein index")
+        data, foff = _fasta_input(blobs)
+        out = _BestCalls()
+        t = _FastaTable()
+        opts = self._opts()
+        _check(lib().skm_annotate_fasta_best(self.db._h, _ptr(data), _ptr(foff), len(foff) - 1, C.byref(opts),
+                                             self.tables()._h, C.byref(out), C.byref(t)))
+        try:
+            self.last_fasta = FastaTable(t)
+        finally:
+            lib().skm_fasta_table_free(C.byref(t))
+        return _best_result(out, self.tables())
 
     def find_best_call(self, calls: np.ndarray):
         """find_best_call (call_functions.tcc:347-659) -> (function_index, function, score, offset)."""

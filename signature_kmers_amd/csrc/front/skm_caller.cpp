@@ -56,6 +56,23 @@ void set_boost_math_modes(int mean_mode, int mad_mode) {
     g_mad_mode = mad_mode;
 }
 
+bool best_call_tables(const std::string& mode, const std::vector<std::string>& function_index, int device,
+                      skm_fidx** fx, std::string& err) {
+    *fx = nullptr;
+    if (mode == "host") return true;
+    if (mode != "device") {
+        err = "--best-call must be host or device";
+        return false;
+    }
+    std::vector<const char*> p(function_index.size());
+    for (size_t i = 0; i < function_index.size(); ++i) p[i] = function_index[i].c_str();
+    if (skm_fidx_create(fx, p.data(), p.size(), device)) {
+        err = skm_last_error();
+        return false;
+    }
+    return true;
+}
+
 bool annot_opts_for(const std::vector<std::string>& function_index, bool ignore_hypo, skm_annot_opts& o,
                     std::string& err) {
     auto hit = std::find(function_index.begin(), function_index.end(), "hypothetical protein");
@@ -73,12 +90,17 @@ bool annot_opts_for(const std::vector<std::string>& function_index, bool ignore_
     return true;
 }
 
-int annotate_batch(skm_db* db, const std::vector<const FastaFile*>& files, const skm_annot_opts& o, int n_threads,
-                   skm_calls* calls, std::string& err) {
-    *calls = skm_calls{};
-    // the batch packed as skm_annotate lays it out on the device (every sequence followed by a 0,
-    // back to back), so the library uploads it as it is instead of packing a second copy; files
-    // are copied by the host threads
+namespace {
+// a batch packed as skm_annotate lays it out on the device (every sequence followed by a 0, back
+// to back), so the library uploads it as it is instead of packing a second copy; files are
+// copied by the host threads
+struct PackedBatch {
+    std::unique_ptr<uint8_t[]> res;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+};
+
+void pack_batch(const std::vector<const FastaFile*>& files, int n_threads, PackedBatch& b) {
     std::vector<uint64_t> rbase(files.size() + 1, 0), sbase(files.size() + 1, 0);
     for (size_t f = 0; f < files.size(); ++f) {
         uint64_t nb = 0;
@@ -86,9 +108,12 @@ int annotate_batch(skm_db* db, const std::vector<const FastaFile*>& files, const
         rbase[f + 1] = rbase[f] + nb;
         sbase[f + 1] = sbase[f] + files[f]->size();
     }
-    std::unique_ptr<uint8_t[]> res(new uint8_t[std::max<uint64_t>(rbase.back(), 1)]);
-    std::vector<uint64_t> off(sbase.back());
-    std::vector<uint32_t> len(sbase.back());
+    b.res.reset(new uint8_t[std::max<uint64_t>(rbase.back(), 1)]);
+    b.off.resize(sbase.back());
+    b.len.resize(sbase.back());
+    std::unique_ptr<uint8_t[]>& res = b.res;
+    std::vector<uint64_t>& off = b.off;
+    std::vector<uint32_t>& len = b.len;
     std::atomic<size_t> nextf{0};
     auto cp = [&]() {
         for (size_t f; (f = nextf.fetch_add(1)) < files.size();) {
@@ -107,7 +132,40 @@ int annotate_batch(skm_db* db, const std::vector<const FastaFile*>& files, const
     for (int t = 1; t < std::max(1, std::min<int>(n_threads, (int)files.size())); ++t) th.emplace_back(cp);
     cp();
     for (auto& t : th) t.join();
-    const int rc = skm_annotate(db, res.get(), off.data(), len.data(), off.size(), &o, calls);
+}
+
+// the device's records against the headers-only host parse, file by file
+int check_fasta_table(const skm_fasta_table& tab, const std::vector<const FastaFile*>& files, std::string& err) {
+    for (size_t f = 0; f < files.size(); ++f) {
+        const uint64_t r0 = tab.file_rec[f], nr = tab.file_rec[f + 1] - r0;
+        bool same = nr == files[f]->size();
+        for (size_t r = 0; same && r < nr; ++r) same = tab.seq_len[r0 + r] == files[f]->len[r];
+        if (!same) {
+            err = "device FASTA parse differs from the host parse of " + files[f]->path + " (" + std::to_string(nr) +
+                  " records on the device, " + std::to_string(files[f]->size()) + " on the host, or other lengths)";
+            return SKM_E_STATE;
+        }
+    }
+    return SKM_OK;
+}
+}  // namespace
+
+int annotate_batch(skm_db* db, const std::vector<const FastaFile*>& files, const skm_annot_opts& o, int n_threads,
+                   skm_calls* calls, std::string& err) {
+    *calls = skm_calls{};
+    PackedBatch b;
+    pack_batch(files, n_threads, b);
+    const int rc = skm_annotate(db, b.res.get(), b.off.data(), b.len.data(), b.off.size(), &o, calls);
+    if (rc) err = skm_last_error();
+    return rc;
+}
+
+int annotate_batch_best(skm_db* db, const std::vector<const FastaFile*>& files, const skm_annot_opts& o, int n_threads,
+                        const skm_fidx* fx, skm_best_calls* best, std::string& err) {
+    *best = skm_best_calls{};
+    PackedBatch b;
+    pack_batch(files, n_threads, b);
+    const int rc = skm_annotate_best(db, b.res.get(), b.off.data(), b.len.data(), b.off.size(), &o, fx, best);
     if (rc) err = skm_last_error();
     return rc;
 }
@@ -121,19 +179,25 @@ int annotate_batch_fasta(skm_db* db, const std::vector<const FastaFile*>& files,
         err = skm_last_error();
         return rc;
     }
-    // the device's records against the headers-only host parse, file by file
-    for (size_t f = 0; f < files.size() && !rc; ++f) {
-        const uint64_t r0 = tab.file_rec[f], nr = tab.file_rec[f + 1] - r0;
-        bool same = nr == files[f]->size();
-        for (size_t r = 0; same && r < nr; ++r) same = tab.seq_len[r0 + r] == files[f]->len[r];
-        if (!same) {
-            err = "device FASTA parse differs from the host parse of " + files[f]->path + " (" + std::to_string(nr) +
-                  " records on the device, " + std::to_string(files[f]->size()) + " on the host, or other lengths)";
-            rc = SKM_E_STATE;
-        }
-    }
+    rc = check_fasta_table(tab, files, err);
     skm_fasta_table_free(&tab);
     if (rc) skm_calls_free(calls);
+    return rc;
+}
+
+int annotate_batch_fasta_best(skm_db* db, const std::vector<const FastaFile*>& files, const uint8_t* bytes,
+                              const uint64_t* file_off, const skm_annot_opts& o, const skm_fidx* fx, skm_best_calls* best,
+                              std::string& err) {
+    *best = skm_best_calls{};
+    skm_fasta_table tab{};
+    int rc = skm_annotate_fasta_best(db, bytes, file_off, files.size(), &o, fx, best, &tab);
+    if (rc) {
+        err = skm_last_error();
+        return rc;
+    }
+    rc = check_fasta_table(tab, files, err);
+    skm_fasta_table_free(&tab);
+    if (rc) skm_best_calls_free(best);
     return rc;
 }
 
@@ -180,11 +244,56 @@ int best_calls_batch(const skm_calls& calls, const std::vector<const FastaFile*>
     return first_rc;
 }
 
+int compose_best_batch(const skm_best_calls& best, const std::vector<const FastaFile*>& files, const skm_fidx* fx,
+                       int n_threads, const std::vector<std::vector<SeqCall>*>& out, std::string& err) {
+    std::vector<std::pair<size_t, size_t>> where;  // (file, record) per batch sequence
+    for (size_t f = 0; f < files.size(); ++f)
+        for (size_t r = 0; r < files[f]->size(); ++r) where.emplace_back(f, r);
+    if (where.size() != best.n_seqs) {
+        err = "best calls: the result does not match the batch";
+        return SKM_E_STATE;
+    }
+    std::atomic<size_t> next{0};
+    std::atomic<int> first_rc{0};
+    auto work = [&]() {
+        std::vector<char> fb(1 << 16);
+        const size_t chunk = 4096;
+        for (size_t s0; (s0 = next.fetch_add(chunk)) < where.size();) {
+            for (size_t s = s0; s < std::min(where.size(), s0 + chunk); ++s) {
+                SeqCall& c = (*out[where[s].first])[where[s].second];
+                const skm_best_call& b = best.best[s];
+                c.fi = b.fi;
+                c.score = b.score;
+                if (b.fi == 0xFFFF && !(b.flags & SKM_BEST_PAIR)) {  // name(0xFFFF) is ""
+                    c.func.clear();
+                    continue;
+                }
+                int n = skm_best_call_name(fx, &b, fb.data(), fb.size());
+                if (n >= (int)fb.size()) {
+                    fb.resize((size_t)n + 1);
+                    n = skm_best_call_name(fx, &b, fb.data(), fb.size());
+                }
+                if (n < 0) first_rc = n;
+                c.func = fb.data();
+            }
+        }
+    };
+    const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_threads), where.size() / 4096 + 1));
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+    if (first_rc) err = "skm_best_call_name failed";
+    return first_rc;
+}
+
 int call_files(skm_db* db, const std::vector<const FastaFile*>& files, const std::vector<std::string>& function_index,
                bool ignore_hypo, int n_threads, std::vector<std::vector<SeqCall>>& out, std::string& err,
-               double* device_ms, uint64_t max_batch_residues, double* host_ms, const FastaBytes* raw) {
+               double* device_ms, uint64_t max_batch_residues, double* host_ms, const FastaBytes* raw,
+               const skm_fidx* fx, uint64_t* n_deferred) {
     const auto t_begin = std::chrono::steady_clock::now();
     double dev_ms = 0;
+    uint64_t deferred = 0;
     skm_annot_opts o{};
     if (!annot_opts_for(function_index, ignore_hypo, o, err)) return SKM_E_ARG;
     std::vector<const char*> fidx(function_index.size());
@@ -200,26 +309,36 @@ int call_files(skm_db* db, const std::vector<const FastaFile*>& files, const std
             nres += files[f1++]->n_residues;
         const std::vector<const FastaFile*> batch(files.begin() + f0, files.begin() + f1);
         skm_calls calls{};
+        skm_best_calls best{};  // fx: find_best_call on the device too, 16 B per sequence come back
         auto t0 = std::chrono::steady_clock::now();
         int rc;
         if (raw) {  // the batch's files as they lie in raw, their offsets from the first one's start
             std::vector<uint64_t> off(raw->file_off.begin() + f0, raw->file_off.begin() + f1 + 1);
             const uint64_t base = off[0];
             for (auto& x : off) x -= base;
-            rc = annotate_batch_fasta(db, batch, raw->bytes.get() + base, off.data(), o, &calls, err);
+            rc = fx ? annotate_batch_fasta_best(db, batch, raw->bytes.get() + base, off.data(), o, fx, &best, err)
+                    : annotate_batch_fasta(db, batch, raw->bytes.get() + base, off.data(), o, &calls, err);
         } else {
-            rc = annotate_batch(db, batch, o, n_threads, &calls, err);
+            rc = fx ? annotate_batch_best(db, batch, o, n_threads, fx, &best, err)
+                    : annotate_batch(db, batch, o, n_threads, &calls, err);
         }
         dev_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (rc) return rc;
         std::vector<std::vector<SeqCall>*> outp;
         for (size_t f = f0; f < f1; ++f) outp.push_back(&out[f]);
-        rc = best_calls_batch(calls, batch, fidx, n_threads, outp, err);
-        skm_calls_free(&calls);
+        if (fx) {
+            deferred += best.n_deferred;
+            rc = compose_best_batch(best, batch, fx, n_threads, outp, err);
+            skm_best_calls_free(&best);
+        } else {
+            rc = best_calls_batch(calls, batch, fidx, n_threads, outp, err);
+            skm_calls_free(&calls);
+        }
         if (rc) return rc;
         f0 = f1;
     }
     if (device_ms) *device_ms = dev_ms;
+    if (n_deferred) *n_deferred = deferred;
     if (host_ms)
         *host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() - dev_ms;
     return SKM_OK;

@@ -1,6 +1,7 @@
 // skm_caller.h -- FunctionCaller<KmerDb>::process_fasta_stream for the CLIs
 // (call_functions.tcc:109-257): every record with a non-empty id is one query; the windows are
-// looked up and the HitSet calls made on the GPU (skm_annotate), find_best_call runs on the host.
+// looked up and the HitSet calls made on the GPU (skm_annotate), find_best_call runs on the host
+// or -- the CLIs' --best-call device -- on the resident calls (skm_annotate_best).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -33,10 +34,18 @@ void set_boost_math_modes(int mean_mode, int mad_mode);
 // are then parsed on the device (annotate_batch_fasta) and the files need no residues.
 // device_ms: wall ms in skm_annotate (packing, upload, device pipeline, calls download);
 // host_ms: wall ms of the rest (batch assembly, find_best_call on n_threads host threads).
+// fx (best_call_tables, --best-call device): find_best_call runs on the device after the HitSet
+// kernels (skm_annotate_best / skm_annotate_fasta_best) and the host only composes the names;
+// *n_deferred = the sequences the device left to skm_find_best_call (0 without fx).
 int call_files(skm_db* db, const std::vector<const FastaFile*>& files, const std::vector<std::string>& function_index,
                bool ignore_hypo, int n_threads, std::vector<std::vector<SeqCall>>& out, std::string& err,
                double* device_ms = nullptr, uint64_t max_batch_residues = 2000000000ull, double* host_ms = nullptr,
-               const FastaBytes* raw = nullptr);
+               const FastaBytes* raw = nullptr, const skm_fidx* fx = nullptr, uint64_t* n_deferred = nullptr);
+
+// --best-call host|device: device makes the function-index tables on `device` (release them with
+// skm_fidx_destroy), host leaves *fx null; false with err for any other word or a failed upload
+bool best_call_tables(const std::string& mode, const std::vector<std::string>& function_index, int device,
+                      skm_fidx** fx, std::string& err);
 
 // The two halves of call_files, for callers that pipeline them (kmers-call-functions overlaps
 // parsing, the device and find_best_call over groups of files, as the reference overlaps its
@@ -55,6 +64,16 @@ int annotate_batch(skm_db* db, const std::vector<const FastaFile*>& files, const
 // record counts and lengths must equal theirs (else SKM_E_STATE, err names the file).
 int annotate_batch_fasta(skm_db* db, const std::vector<const FastaFile*>& files, const uint8_t* bytes,
                          const uint64_t* file_off, const skm_annot_opts& o, skm_calls* calls, std::string& err);
+// the two device halves with find_best_call on the resident calls: *best is released with
+// skm_best_calls_free
+int annotate_batch_best(skm_db* db, const std::vector<const FastaFile*>& files, const skm_annot_opts& o, int n_threads,
+                        const skm_fidx* fx, skm_best_calls* best, std::string& err);
+int annotate_batch_fasta_best(skm_db* db, const std::vector<const FastaFile*>& files, const uint8_t* bytes,
+                              const uint64_t* file_off, const skm_annot_opts& o, const skm_fidx* fx, skm_best_calls* best,
+                              std::string& err);
+// their host half: name composition only (skm_best_call_name) on n_threads threads
+int compose_best_batch(const skm_best_calls& best, const std::vector<const FastaFile*>& files, const skm_fidx* fx,
+                       int n_threads, const std::vector<std::vector<SeqCall>*>& out, std::string& err);
 // the host half: find_best_call per sequence on n_threads threads; out[f] is the call vector of
 // files[f] (sized by the caller)
 int best_calls_batch(const skm_calls& calls, const std::vector<const FastaFile*>& files,

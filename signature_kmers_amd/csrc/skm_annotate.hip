@@ -1010,6 +1010,7 @@ struct skm_query {
     bool ran = false;
     std::unique_ptr<HostPool> pool;  // packs the residues (created on first use)
     std::unique_ptr<FastaWork> fasta;  // the device FASTA parser's buffers, the raw bytes among them
+    BestWork best;  // skm_query_best_calls: scratch and results of the best-call kernel
 };
 
 namespace {
@@ -1779,6 +1780,45 @@ int skm_annotate_fasta(skm_db* db, const uint8_t* bytes, const uint64_t* file_of
     int rc = annotate_setup_fasta(db, bytes, file_off, n_files, tab);
     if (!rc) rc = skm_query_run(db->aq, opts);
     if (!rc) rc = skm_query_calls(db->aq, calls);
+    if (rc && tab) skm_fasta_table_free(tab);
+    return rc;
+}
+
+// find_best_call on the resident calls of the last run (skm_bestcall.hip): 16 B per sequence come
+// back instead of 24 B per call + 8 B per sequence
+int skm_query_best_calls(skm_query* q, const skm_fidx* fx, skm_best_calls* out) {
+    SKM_API_BEGIN
+    SKM_CHECK(q && fx && out, SKM_E_ARG, "null argument");
+    SKM_CHECK(q->ran, SKM_E_STATE, "skm_query_run has not been called");
+    SKM_HIP(hipSetDevice(q->db->device));
+    best_calls_resident(q->d_calls.as<skm_kmer_call>(), q->d_call_off.as<uint64_t>(), q->nseq, q->n_calls, fx,
+                        q->db->device, q->stream, q->best, out);
+    out->n_windows = q->n_windows;
+    SKM_API_END
+}
+
+int skm_annotate_best(skm_db* db, const uint8_t* residues, const uint64_t* seq_off, const uint32_t* seq_len, size_t n_seqs,
+                      const skm_annot_opts* opts, const skm_fidx* fx, skm_best_calls* out) {
+    if (!fx || !out) {
+        set_last_error("null argument");
+        return SKM_E_ARG;
+    }
+    int rc = annotate_setup(db, residues, seq_off, seq_len, n_seqs);
+    if (!rc) rc = skm_query_run(db->aq, opts);
+    if (!rc) rc = skm_query_best_calls(db->aq, fx, out);
+    return rc;
+}
+
+int skm_annotate_fasta_best(skm_db* db, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                            const skm_annot_opts* opts, const skm_fidx* fx, skm_best_calls* out, skm_fasta_table* tab) {
+    if (tab) std::memset(tab, 0, sizeof(*tab));
+    if (!opts || !fx || !out) {
+        set_last_error("null argument");
+        return SKM_E_ARG;
+    }
+    int rc = annotate_setup_fasta(db, bytes, file_off, n_files, tab);
+    if (!rc) rc = skm_query_run(db->aq, opts);
+    if (!rc) rc = skm_query_best_calls(db->aq, fx, out);
     if (rc && tab) skm_fasta_table_free(tab);
     return rc;
 }

@@ -100,6 +100,17 @@ inline void alloc_reported(DevBuf& buf, uint64_t bytes, const char* what) {
     buf.bytes = bytes;
 }
 
+// the best-call kernel over a resident CSR of calls (skm_bestcall.hip): scratch for the collapsed
+// lists and the results, kept by whoever owns the calls.  best_calls_resident fills *out (best,
+// n_seqs, n_calls, n_deferred, kernel_ms), resolving deferred sequences on the host.
+struct BestWork {
+    DevBuf d_work, d_best;
+    hipEvent_t ev[2] = {};
+    ~BestWork();
+};
+void best_calls_resident(const skm_kmer_call* d_calls, const uint64_t* d_call_off, uint64_t n_seqs, uint64_t n_calls,
+                         const skm_fidx* fx, int device, hipStream_t st, BestWork& w, skm_best_calls* out);
+
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 inline int ilog2_ceil(uint64_t x) {
     int b = 0;

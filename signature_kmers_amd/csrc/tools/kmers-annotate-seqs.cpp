@@ -9,7 +9,9 @@
 // reference was compiled against, call_functions.tcc:51-53: current = >= 1.76, legacy = the older
 // single running mean and |x(mid)| MAD); --fasta-parse host|device (device: the files' bytes are
 // kept, the host parses headers only and the device parses the sequence bodies in HBM,
-// skm_annotate_fasta; same output bytes and error reports).
+// skm_annotate_fasta; same output bytes and error reports); --best-call host|device (device:
+// find_best_call runs on the device's resident calls, skm_annotate_best, and the host composes the
+// names; same output bytes).
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -42,7 +44,7 @@ int main(int argc, char** argv) {
                 {"uncalled-ids-file", 0, false, false}, {"parallel", 'j', false, false},
                 {"ignore-hypo", 0, true, false},      {"help", 'h', true, false},
                 {"device", 0, false, false}, {"boost-math-stats", 0, false, false},
-                {"fasta-parse", 0, false, false}};
+                {"fasta-parse", 0, false, false}, {"best-call", 0, false, false}};
     op.positional = {"kmer-data-dir", "genus-data-dir", "sequences-dir", "calls-file", "uncalled-ids-file"};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
@@ -59,6 +61,7 @@ int main(int argc, char** argv) {
                   << "  --device arg                  HIP device ordinal (default 0)\n"
                   << "  --boost-math-stats arg          current (default) | legacy Boost.Math mean/MAD\n"
                   << "  --fasta-parse arg             host (default) | device: where the sequence bodies are parsed\n"
+                  << "  --best-call arg               host (default) | device: where find_best_call runs\n"
                   << "  -h [ --help ]                 show this help message\n\n";
         return 0;
     }
@@ -72,6 +75,8 @@ int main(int argc, char** argv) {
     const std::string fasta_parse = op.get("fasta-parse", "host");
     if (fasta_parse != "host" && fasta_parse != "device") die("--fasta-parse must be host or device");
     const bool parse_on_device = fasta_parse == "device";
+    const std::string best_call = op.get("best-call", "host");
+    if (best_call != "host" && best_call != "device") die("--best-call must be host or device");
     const int device = std::atoi(op.get("device", "0").c_str());
     const std::string data_dir = op.get("kmer-data-dir");
     const std::string db_base = path_join(data_dir, "kmer_data");
@@ -92,9 +97,12 @@ int main(int argc, char** argv) {
     std::vector<const FastaFile*> fptr;
     for (auto& f : files) fptr.push_back(&f);
     std::vector<std::vector<SeqCall>> calls;
+    skm_fidx* fx = nullptr;
+    if (!best_call_tables(best_call, fidx, device, &fx, err)) die(err);
     if (call_files(db, fptr, fidx, op.has("ignore-hypo"), n_threads, calls, err, nullptr, 2000000000ull, nullptr,
-                   parse_on_device ? &raw : nullptr))
+                   parse_on_device ? &raw : nullptr, fx))
         die(err);
+    skm_fidx_destroy(fx);
     skm_db_close(db);
 
     std::ofstream anno(op.get("calls-file"));

@@ -179,7 +179,7 @@ int main(int argc, char** argv) {
                 {"dump-extract", 0, false, false},     {"mph-seed", 0, false, false},
                 {"n-gpus", 0, false, false},           {"comm", 0, false, false},
                 {"comm-file", 0, false, false},        {"recall-db", 0, false, false},
-                {"perfect-hash-source", 0, false, false}};
+                {"perfect-hash-source", 0, false, false}, {"best-call", 0, false, false}};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
     if (op.has("help")) {
@@ -206,6 +206,7 @@ int main(int argc, char** argv) {
                   << "  --perfect-hash-source arg            host (default): the perfect hash from the downloaded kept k-mers;\n"
                   << "                                       device: hash and data files written from the DB built on the GPU\n"
                   << "                                       from the build's resident kept k-mers (needs --perfect-hash, one GPU)\n"
+                  << "  --best-call arg                      host (default) | device: where the recall pass runs find_best_call\n"
                   << "  -h [ --help ]                        show this help message\n";
         return 1;
     }
@@ -221,6 +222,8 @@ int main(int argc, char** argv) {
     const bool launched = env_ws && std::atoi(env_ws) > 1 && !op.has("n-gpus");
     if (recall_db == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
         die("--recall-db device needs one GPU: the kept k-mers of a multi-rank build are sharded over the ranks");
+    const std::string best_call = op.get("best-call", "host");
+    if (best_call != "host" && best_call != "device") die("--best-call must be host or device");
     const std::string ph_source = op.get("perfect-hash-source", "host");
     if (ph_source != "host" && ph_source != "device") die("--perfect-hash-source must be host or device");
     if (ph_source == "device" && op.get("perfect-hash").empty())
@@ -544,7 +547,13 @@ int main(int argc, char** argv) {
     for (auto& f : files) fptr.push_back(&f);
     std::vector<std::vector<SeqCall>> calls;
     double recall_dev_ms = 0;
-    if (call_files(kdb, fptr, fidx, false, n_threads, calls, err, &recall_dev_ms)) die(err);
+    uint64_t recall_deferred = 0;
+    skm_fidx* fx = nullptr;  // --best-call device: find_best_call on the recall's resident calls
+    if (!best_call_tables(best_call, fidx, device, &fx, err)) die(err);
+    if (call_files(kdb, fptr, fidx, false, n_threads, calls, err, &recall_dev_ms, 2000000000ull, nullptr, nullptr, fx,
+                   &recall_deferred))
+        die(err);
+    skm_fidx_destroy(fx);
     skm_db_close(kdb);
     {  // one report per file (kmers-build-signatures.cc:300-349), the files on the host threads
         std::atomic<size_t> next_f{0};
@@ -593,7 +602,7 @@ int main(int argc, char** argv) {
               << " finish " << t_finish << " final_kmers " << t_final_kmers << " mph " << t_mph << " recall "
               << t_recall << " recall_device " << t_recall_dev << " total " << now_s() - t_start << " startup "
               << t_startup << " defs " << t_defs << " hip_init " << t_hip_init << " create " << t_create
-              << " parse_files " << t_files << " fm_load " << t_fm << "\n";
+              << " parse_files " << t_files << " fm_load " << t_fm << " recall_deferred " << recall_deferred << "\n";
     std::cerr << "all done\n";
     fast_exit(0);  // every output file is closed by now
 }

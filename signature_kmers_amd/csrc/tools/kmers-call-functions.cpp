@@ -12,7 +12,9 @@
 // reference was compiled against, call_functions.tcc:51-53: current = >= 1.76, legacy = the older
 // single running mean and |x(mid)| MAD); --fasta-parse host|device (device: the parse stage keeps
 // the files' bytes and parses headers only, the device stage parses the sequence bodies in HBM,
-// skm_annotate_fasta; same output bytes and error reports).
+// skm_annotate_fasta; same output bytes and error reports); --best-call host|device (device: the
+// device stage also runs find_best_call on the resident calls, skm_annotate_best /
+// skm_annotate_fasta_best, and the host stage composes names and formats lines; same output bytes).
 #include <sys/stat.h>
 
 #include <cmath>
@@ -93,7 +95,7 @@ int main(int argc, char** argv) {
     op.specs = {{"data-dir", 'd', false, false}, {"input-files", 'i', false, true}, {"output-files", 'o', false, false},
                 {"n-threads", 'j', false, false}, {"ignore-hypo", 0, true, false},  {"debug-hits", 0, true, false},
                 {"help", 'h', true, false},       {"device", 0, false, false}, {"boost-math-stats", 0, false, false},
-                {"fasta-parse", 0, false, false}};
+                {"fasta-parse", 0, false, false}, {"best-call", 0, false, false}};
     op.positional = {"data-dir", "input-files"};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
@@ -108,6 +110,7 @@ int main(int argc, char** argv) {
                   << "  --device arg                HIP device ordinal (default 0)\n"
                   << "  --boost-math-stats arg        current (default) | legacy Boost.Math mean/MAD\n"
                   << "  --fasta-parse arg           host (default) | device: where the sequence bodies are parsed\n"
+                  << "  --best-call arg             host (default) | device: where find_best_call runs\n"
                   << "  -h [ --help ]               show this help message\n\n";
     };
     if (op.has("help")) {
@@ -133,6 +136,8 @@ int main(int argc, char** argv) {
     if (fasta_parse != "host" && fasta_parse != "device") die("--fasta-parse must be host or device");
     const bool parse_on_device = fasta_parse == "device";
     if (parse_on_device && op.has("debug-hits")) die("--debug-hits needs the residues of --fasta-parse host");
+    const std::string best_call = op.get("best-call", "host");
+    if (best_call != "host" && best_call != "device") die("--best-call must be host or device");
     const int device = std::atoi(op.get("device", "0").c_str());
     // the HIP runtime initialises on a thread of its own while the DB files are read (the first
     // HIP call of a process costs ~0.1-0.3 s; skm_db_open's uploads then find it done)
@@ -181,6 +186,7 @@ int main(int argc, char** argv) {
         FastaBytes raw;  // --fasta-parse device: the files' bytes, until the device stage has taken them
         std::vector<std::vector<SeqCall>> calls;
         skm_calls dev{};
+        skm_best_calls best{};  // --best-call device: the device stage's result instead of dev
         std::string text;
         int state = 0;  // 1 parsed, 2 on-device done, 3 calls + text ready; -1 failed
         std::string err;
@@ -222,9 +228,12 @@ int main(int argc, char** argv) {
             set_state(g, 1);
         }
     });
+    skm_fidx* fx = nullptr;  // --best-call device: the function-index tables on the device
+    uint64_t n_deferred = 0;
     std::thread device_stage([&] {
         db_thread.join();
         hip_warm.join();
+        if (db_err.empty() && !best_call_tables(best_call, fidx, device, &fx, db_err)) fx = nullptr;
         for (size_t g = 0; g < ng; ++g) {
             if (!db_err.empty()) {
                 set_state(g, -1, db_err);
@@ -236,11 +245,19 @@ int main(int argc, char** argv) {
             for (auto& f : groups[g].files) fp.push_back(&f);
             std::string e;
             Group& G = groups[g];
-            if (parse_on_device ? annotate_batch_fasta(db, fp, G.raw.bytes.get(), G.raw.file_off.data(), aopts, &G.dev, e)
-                                : annotate_batch(db, fp, aopts, n_threads, &G.dev, e)) {
+            int rc;
+            if (fx)
+                rc = parse_on_device ? annotate_batch_fasta_best(db, fp, G.raw.bytes.get(), G.raw.file_off.data(), aopts, fx,
+                                                                 &G.best, e)
+                                     : annotate_batch_best(db, fp, aopts, n_threads, fx, &G.best, e);
+            else
+                rc = parse_on_device ? annotate_batch_fasta(db, fp, G.raw.bytes.get(), G.raw.file_off.data(), aopts, &G.dev, e)
+                                     : annotate_batch(db, fp, aopts, n_threads, &G.dev, e);
+            if (rc) {
                 set_state(g, -1, e);
                 continue;
             }
+            n_deferred += G.best.n_deferred;
             G.raw = FastaBytes();
             t_dev += secs(t);
             set_state(g, 2);
@@ -260,8 +277,10 @@ int main(int argc, char** argv) {
                 op_.push_back(&G.calls[f]);
             }
             std::string e;
-            const int rc = best_calls_batch(G.dev, fp, fptr_idx, n_threads, op_, e);
+            const int rc = fx ? compose_best_batch(G.best, fp, fx, n_threads, op_, e)
+                              : best_calls_batch(G.dev, fp, fptr_idx, n_threads, op_, e);
             skm_calls_free(&G.dev);
+            skm_best_calls_free(&G.best);
             if (rc) {
                 set_state(g, -1, e);
                 continue;
@@ -332,12 +351,13 @@ int main(int argc, char** argv) {
     host_stage.join();
     if (!fail.empty()) die(fail);
     out->flush();
+    skm_fidx_destroy(fx);
     if (db) skm_db_close(db);
     // one machine-readable line of the phases (bench.py's cli_call leg): busy seconds per stage
     // (the stages overlap) and the pipeline's wall time
     std::cerr << "phases: sequences " << nrec << " db_open " << t_open << " parse " << t_parse << " device " << t_dev
               << " best_call " << t_best << " write " << t_write << " groups " << ng << " wall " << secs(t_all)
-              << " startup " << t_startup << "\n";
+              << " startup " << t_startup << " deferred " << n_deferred << "\n";
     if (ofs.is_open()) ofs.close();
     fast_exit(0);
 }
