@@ -3925,10 +3925,10 @@ __global__ __launch_bounds__(BP_THREADS) void k_overflow(BucketArgs A, OvfScratc
             if (tid == 0) {
                 s_base[0] = atomicAdd(A.kept_ctr, (unsigned long long)K);
                 atomicAdd(&A.ctr[0], (unsigned long long)K);  // the overflow's own kept count
-                if (J) {
-                    s_base[1] = atomicAdd(&A.ctr[3], (unsigned long long)J);
-                    s_base[2] = atomicAdd(&A.ctr[4], (unsigned long long)Lt);
-                }
+                if (J) s_base[1] = atomicAdd(&A.ctr[3], (unsigned long long)J);
+                // the inline chains' samples need their range too: a round whose chains all run
+                // inline has no job (J == 0) and still writes Lt lengths
+                if (Lt) s_base[2] = atomicAdd(&A.ctr[4], (unsigned long long)Lt);
                 s_nbig = 0;
             }
             __syncthreads();
