@@ -270,6 +270,17 @@ int skm_build_debug_jobs(skm_build* b, uint32_t* out, int cap);
 /* Diagnostics: element counts of the last pass's overflow sub-buckets as the partition listed
  * them; returns how many there are (at most cap written). */
 int skm_build_debug_overflow(skm_build* b, uint32_t* out, int cap);
+/* Diagnostics (read-only, after a run): the geometry of the extraction front end, at most cap of
+ * out[0..11) = residue bytes with separators (rp), emission rows (sel_wg), windows per emission
+ * row (sel_span), passes emitted per residue scan (emit_g), the staged scatter's span and
+ * workgroups over a pass's position list (pf_span, pf_nwg), the one-pass extract workgroups and
+ * their span (nwg, span), pass_bits, owner_bits, b1_bits.  The five key-range-pass values
+ * (sel_wg .. pf_nwg) are 0 after a one-pass run.  Returns 11, SKM_E_STATE without a completed run. */
+int skm_build_debug_front(skm_build* b, uint64_t* out, int cap);
+/* Diagnostics (read-only, after a run): this rank's window count of every key-range pass of the
+ * last run, after any heavy-key routing (at most cap written); returns the pass count.  With one
+ * pass: the single valid window count. */
+int skm_build_debug_pass_windows(skm_build* b, uint64_t* out, int cap);
 /* Diagnostics: device time of the chain kernel on njobs synthetic jobs of length n
  * (mode 0: the build's choice by length, 1: one lane per chain, 2: one wave pair per chain;
  *  3 / 5: the P^2 wave alone, previous / current walk; 4: the variance wave alone). */

@@ -133,6 +133,8 @@ _SIGS = {
     "skm_build_reserve": (C.c_int, [_P, C.c_uint64, C.c_uint64]),
     "skm_build_debug_jobs": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_int]),
     "skm_build_debug_overflow": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_int]),
+    "skm_build_debug_front": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
+    "skm_build_debug_pass_windows": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     "skm_debug_chain_bench": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_float)]),
     "skm_debug_chain_eval": (C.c_int, [_P, C.c_uint32, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "skm_build_debug_stamps": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64), C.c_int]),
@@ -431,6 +433,25 @@ class SignatureBuilder:
         v = (C.c_uint32 * k)()
         n = lib().skm_build_debug_overflow(self._h, v, k)
         return [int(x) for x in v[:min(max(n, 0), k)]]
+
+    def debug_front(self) -> dict:
+        """skm_build_debug_front: the geometry of the last run's extraction front end (the
+        key-range-pass fields are 0 after a one-pass run)."""
+        names = ["rp", "sel_wg", "sel_span", "emit_g", "pf_span", "pf_nwg", "nwg", "span", "pass_bits",
+                 "owner_bits", "b1_bits"]
+        v = (C.c_uint64 * len(names))()
+        n = lib().skm_build_debug_front(self._h, v, len(names))
+        _check(min(n, 0))
+        assert n == len(names), n
+        return {names[i]: int(v[i]) for i in range(n)}
+
+    def debug_pass_windows(self) -> list:
+        """skm_build_debug_pass_windows: this rank's windows of every key-range pass of the last run
+        (one value, the valid windows, after a one-pass run)."""
+        v = (C.c_uint64 * 64)()
+        n = lib().skm_build_debug_pass_windows(self._h, v, 64)
+        _check(min(n, 0))
+        return [int(x) for x in v[:n]]
 
     def debug_stamps(self, enable: bool) -> list:
         v = (C.c_uint64 * 32)()

@@ -6054,14 +6054,23 @@ void size_arena(skm_build* b) {
     // free for this plan too (counting them as used shrank the cap below the kept count)
     const uint64_t held = (uint64_t)b->d_keys.bytes + (uint64_t)b->d_data.bytes;
     const uint64_t avail = fr + held > reserve ? fr + held - reserve : 0;
-    uint64_t cap = std::min<uint64_t>(b->valid_total + 16, avail / (8 + sizeof(skm_stored_kmer_data)));
+    // a rank keeps at most one k-mer per element it groups: its own valid windows, or at world > 1
+    // what it receives over all passes (pass_peer_counts) -- a rank with few windows of its own
+    // still owns its share of the other ranks' keys
+    uint64_t owned = b->valid_total, most = b->pass_max;
+    if (b->world > 1) {
+        owned = 0;
+        for (const uint64_t v : b->xs_recv) owned += v;
+        most = std::max<uint64_t>(most, b->n_local_max);
+    }
+    uint64_t cap = std::min<uint64_t>(owned + 16, avail / (8 + sizeof(skm_stored_kmer_data)));
     if (b->tune.mem_budget_mb > 0) {
         const uint64_t budget = (uint64_t)b->tune.mem_budget_mb << 20;
         const bool giant = b->tune.giant_class > 0 || (b->tune.giant_class < 0 && (b->pass_bits == 0 || b->world > 1));
         const uint64_t used = pass_work(b->pass_max, b->pass_bits, b->rp, giant);
         cap = std::min<uint64_t>(cap, budget > used ? (budget - used) / 18 : 0);
     }
-    cap = std::max<uint64_t>(cap, b->pass_max + 16);
+    cap = std::max<uint64_t>(cap, most + 16);
     b->d_keys.ensure(8 * cap);
     b->d_data.ensure(sizeof(skm_stored_kmer_data) * cap + 16);
     b->kept_cap = cap;
@@ -7855,6 +7864,44 @@ int skm_build_debug_overflow(skm_build* b, uint32_t* out, int cap) {
     if (n && hipMemcpy(e.data(), b->d_ovf.p, sizeof(OvfEntry) * n, hipMemcpyDeviceToHost) != hipSuccess) return SKM_E_HIP;
     for (int i = 0; i < cap; ++i) out[i] = (uint32_t)i < n ? e[i].n : 0u;
     return (int)n;
+}
+
+// Diagnostics: the geometry the last run's extraction front end worked with (the key-range-pass
+// fields are 0 after a one-pass run); returns how many values there are (11).
+int skm_build_debug_front(skm_build* b, uint64_t* out, int cap) {
+    if (!b || !out) return SKM_E_ARG;
+    if (!b->ran) return SKM_E_STATE;
+    const bool passes = b->pass_bits > 0;
+    const uint64_t v[11] = {b->rp,
+                            passes ? b->sel_wg : 0ull,
+                            passes ? b->sel_span : 0ull,
+                            passes ? b->emit_g : 0ull,
+                            passes ? b->pf_span : 0ull,
+                            passes ? b->pf_nwg : 0ull,
+                            b->nwg,
+                            b->span,
+                            (uint64_t)b->pass_bits,
+                            (uint64_t)b->owner_bits,
+                            (uint64_t)b->b1_bits};
+    for (int i = 0; i < cap && i < 11; ++i) out[i] = v[i];
+    return 11;
+}
+
+// Diagnostics: the window count of every key-range pass of the last run (k_sel_scan's npos, after
+// any routing) -- this rank's windows, before the exchange; returns the pass count P.  With one pass
+// there is no position list: the one value is the valid window count of prepare's scan.
+int skm_build_debug_pass_windows(skm_build* b, uint64_t* out, int cap) {
+    if (!b || !out) return SKM_E_ARG;
+    if (!b->ran) return SKM_E_STATE;
+    if (hipSetDevice(b->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return SKM_E_HIP;
+    const uint32_t P = 1u << b->pass_bits;
+    std::vector<uint64_t> n(P, b->pass_max);
+    if (b->pass_bits) {
+        if (!b->d_npos.p || b->d_npos.bytes < 8ull * P) return SKM_E_STATE;
+        if (hipMemcpy(n.data(), b->d_npos.p, 8ull * P, hipMemcpyDeviceToHost) != hipSuccess) return SKM_E_HIP;
+    }
+    for (int i = 0; i < cap && (uint32_t)i < P; ++i) out[i] = n[i];
+    return (int)P;
 }
 
 // Diagnostics: time k_chains on `njobs` synthetic jobs of length n (lengths 300 +- 60).
