@@ -258,7 +258,8 @@ int skm_debug_transport_check(const skm_transport* tp, int rank, int world);
  *   first; 1), "big_grid" / "big_grid_large" (k_big_groups' persistent grids),
  *   "emit_group" (key-range passes emitted per residue scan: 0 = 4, or 1, 2, 4, 8, 16),
  *   "handoff_index_limit" / "handoff_max_chunk" (tests: force the hand-off's 64-bit indices /
- *   small chunks).
+ *   small chunks), "final_kmers_piece_kb" (tests: skm_build_write_final_kmers' pinned piece size
+ *   in KB, 1 .. 2^20; 0 = 64 MB).
  * Unknown names and out-of-range values return SKM_E_ARG. */
 int skm_build_set_option(skm_build* b, const char* name, int64_t value);
 /* Diagnostics: copy the per-phase cycle sums of the last run (if enabled) into out, then
@@ -469,6 +470,49 @@ int skm_build_mph_db(skm_build* b, const skm_mph_db_opts* opts, skm_db** out, sk
  * time during skm_build_mph_db, the arena not counted (the peel state: 16 bytes per vertex and 5
  * per key).  n above the BDZ limit returns SKM_E_ARG.  Callers decide on release_work with it. */
 int skm_mph_db_plan(uint64_t n, uint64_t out[4]);
+
+/* final.kmers written from the resident arena, formatted on the device -- the third product of
+ * the kept set (with skm_build_kept_db and skm_build_mph_db) that needs no host copy of it.
+ * Replaces the dump loop of kmers-build-signatures.cc:198-221: one line per kept k-mer,
+ *   KMER '\t' avg_from_end '\t' function_index '\t' '\n'
+ * KMER = the 8 key bytes as they are, the two numbers as decimals without leading zeros; lines in
+ * ascending key order (the order of skm_build_finish; the reference's is hash order). */
+typedef struct skm_final_kmers_stats {
+    uint64_t n_kmers, bytes, chunks, pieces; /* lines, file bytes, key-range chunks, pinned pieces  */
+    double total_s, wait_s, write_s;         /* host seconds: the call, of them waiting for the
+                                                device / PCIe, and in pwrite                      */
+    float select_ms, sort_ms, gather_ms, format_ms, d2h_ms; /* device ms summed over the chunks and
+                                                pieces; gather_ms is 0: the format kernels read
+                                                keys and records through the sorted index       */
+    uint32_t wide_index;                     /* 1: 64-bit arena indices ("handoff_index_limit")   */
+} skm_final_kmers_stats;
+/* kmers-build-signatures.cc:198-221.  Runs the build first if it has not run since prepare (as
+ * skm_build_finish does), then sorts the arena's keys chunk by chunk as the finish hand-off does,
+ * formats each chunk's lines on the device and streams the text through two pinned pieces into
+ * `path` (pwrite at each piece's file offset).  The file is created and truncated before anything
+ * else runs; no kept k-mer gives an empty file.  world_size > 1 returns SKM_E_STATE before that
+ * (no file is made).  An open, write or close error returns SKM_E_IO with the path in
+ * skm_last_error(); the file may then be partial, and b stays usable.  Works on a handle whose
+ * work buffers were released (skm_build_kept_db / skm_build_mph_db release_work).  stats may be
+ * NULL.  Options: "handoff_index_limit" / "handoff_max_chunk" as for the finish hand-off, and
+ * "final_kmers_piece_kb" (tests: the pinned piece size in KB, 1 .. 2^20; 0 = 64 MB). */
+int skm_build_write_final_kmers(skm_build* b, const char* path, skm_final_kmers_stats* stats);
+/* kmers-build-signatures.cc:198-221 (the stdout lines and distinct_functions around the dump):
+ * everything skm_build_finish returns except the arrays -- keys and data are NULL; n,
+ * distinct_functions, seqs_with_func, n_functions, n_seqs_with_signature (distinct seq ids where
+ * they collide, as skm_build_finish counts them), distinct_signatures, n_windows and n_records are
+ * filled.  Runs the build first if needed; works after a release; world_size > 1 returns
+ * SKM_E_STATE.  Free with skm_kept_free. */
+int skm_build_stats(skm_build* b, skm_kept* out);
+/* kmers-build-signatures.cc:198-221 has no geometry (it is a loop over a map); the device
+ * formatter's: lines per emit tile (one workgroup), threads per workgroup, the longest line in
+ * bytes (22), reserved (0).  Host only. */
+int skm_final_kmers_info(uint32_t out[4]);
+/* kmers-build-signatures.cc:198-221 on the host (test hook, no device): the lines of n kept k-mers
+ * through the formatter the device kernels run (csrc/skm_finalkmers.h).  *len = the total length,
+ * also when cap is too small; then only the whole lines that fit in cap bytes are written. */
+int skm_debug_final_kmers_host(const uint64_t* keys, const skm_stored_kmer_data* data, size_t n, uint8_t* out,
+                               size_t cap, uint64_t* len);
 
 /* ------------------------------------------------------------------------------------------
  * Function calling.  Replaces FunctionCaller<CmphKmerDb>::process_aa_seq for a batch of query

@@ -104,6 +104,13 @@ class _MphDbOpts(C.Structure):
                 ("mph_path", C.c_char_p), ("dat_path", C.c_char_p)]
 
 
+class _FinalKmersStats(C.Structure):
+    _fields_ = [("n_kmers", C.c_uint64), ("bytes", C.c_uint64), ("chunks", C.c_uint64), ("pieces", C.c_uint64),
+                ("total_s", C.c_double), ("wait_s", C.c_double), ("write_s", C.c_double),
+                ("select_ms", C.c_float), ("sort_ms", C.c_float), ("gather_ms", C.c_float), ("format_ms", C.c_float),
+                ("d2h_ms", C.c_float), ("wide_index", C.c_uint32)]
+
+
 class _Pairs(C.Structure):
     _fields_ = [("pairs", C.POINTER(C.c_uint32)), ("n", C.c_uint64), ("n_hits", C.c_uint64)]
 
@@ -152,6 +159,10 @@ _SIGS = {
     "skm_debug_kept_slot": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "skm_build_mph_db": (C.c_int, [_P, C.POINTER(_MphDbOpts), C.POINTER(_P), C.c_void_p]),
     "skm_mph_db_plan": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "skm_build_write_final_kmers": (C.c_int, [_P, C.c_char_p, C.POINTER(_FinalKmersStats)]),
+    "skm_build_stats": (C.c_int, [_P, C.POINTER(_Kept)]),
+    "skm_final_kmers_info": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "skm_debug_final_kmers_host": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_uint64)]),
     "skm_db_lookup_fm": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "skm_db_table_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     "skm_db_size": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
@@ -298,6 +309,8 @@ class KeptKmers:
     n_seqs_with_signature: int
     distinct_signatures: int
     n_windows: int
+    n: int = 0                       # kept k-mers (len(keys), except from SignatureBuilder.stats)
+    n_records: int = 0               # valid windows (occurrences)
 
     def stats_lines(self) -> str:
         """stdout of process_kmers (signature_build.tcc:210-212)."""
@@ -505,13 +518,29 @@ class SignatureBuilder:
         db.stats = {n: getattr(st, n) for n, _ in _MphStats._fields_ if n != "pad"}
         return db
 
+    def write_final_kmers(self, path: str) -> dict:
+        """skm_build_write_final_kmers: final.kmers (kmers-build-signatures.cc:198-221) of the last
+        run written to `path` from the resident arena -- sorted, formatted and streamed out by the
+        device, no host copy of the kept set and no finish().  One GPU; works after kept_db / mph_db
+        released the work buffers.  Returns the call's statistics (skm_final_kmers_stats)."""
+        st = _FinalKmersStats()
+        _check(lib().skm_build_write_final_kmers(self._h, os.fsencode(path), C.byref(st)))
+        return {n: getattr(st, n) for n, _ in _FinalKmersStats._fields_}
+
+    def stats(self) -> KeptKmers:
+        """skm_build_stats: what finish() returns without the kept set -- keys and data are empty,
+        `n` is the number of kept k-mers.  One GPU; works after a release."""
+        k = _Kept()
+        _check(lib().skm_build_stats(self._h, C.byref(k)))
+        return self._kept(k)
+
     @staticmethod
     def _kept(k) -> KeptKmers:
         """The library's arrays without a copy: keys / data view the hand-off's host arrays, which
         skm_kept_free releases when the last view is gone."""
         owner = _KeptOwner(k)
         n = int(k.n)
-        if n:
+        if n and k.keys:
             kb = (C.c_char * (8 * n)).from_address(C.cast(k.keys, C.c_void_p).value)
             db = (C.c_char * (10 * n)).from_address(C.cast(k.data, C.c_void_p).value)
             kb._owner = db._owner = owner
@@ -523,7 +552,7 @@ class SignatureBuilder:
         df = np.ctypeslib.as_array(k.distinct_functions, shape=(max(nf, 1),))[:nf].copy()
         sw = np.ctypeslib.as_array(k.seqs_with_func, shape=(max(nf, 1),))[:nf].copy()
         return KeptKmers(keys, data, df, sw, int(k.n_seqs_with_signature), int(k.distinct_signatures),
-                         int(k.n_windows))
+                         int(k.n_windows), int(k.n), int(k.n_records))
 
     def close(self):
         if self._h:
@@ -785,6 +814,27 @@ def mph_db_plan(n: int) -> tuple:
     v = (C.c_uint64 * 4)()
     _check(lib().skm_mph_db_plan(int(n), v))
     return tuple(int(x) for x in v)
+
+
+def final_kmers_info() -> tuple:
+    """skm_final_kmers_info (host only): the device final.kmers formatter's (lines per emit tile,
+    threads per workgroup, longest line in bytes, 0)."""
+    out = (C.c_uint32 * 4)()
+    _check(lib().skm_final_kmers_info(out))
+    return tuple(int(x) for x in out)
+
+
+def final_kmers_host(keys: np.ndarray, data: np.ndarray) -> bytes:
+    """skm_debug_final_kmers_host (host only): the final.kmers lines of (keys, data) through the
+    formatter the device kernels run."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=STORED_DTYPE)
+    assert len(keys) == len(data)
+    n = C.c_uint64()
+    _check(lib().skm_debug_final_kmers_host(_ptr(keys), _ptr(data), len(keys), None, 0, C.byref(n)))
+    out = np.zeros(max(int(n.value), 1), np.uint8)
+    _check(lib().skm_debug_final_kmers_host(_ptr(keys), _ptr(data), len(keys), _ptr(out), int(n.value), C.byref(n)))
+    return out[:int(n.value)].tobytes()
 
 
 def kept_slot(key: int, slots: int) -> int:

@@ -21,9 +21,12 @@
 // Exactness notes: group members are visited in reverse ordinal order
 // (TBB 2020 multimap LIFO), the cut is fp32 `(float)best < (float)count*0.8f`, statistics are
 // the Boost.Accumulators recurrences in fp64 with contraction disabled (-ffp-contract=off).
+#include <fcntl.h>
 #include <hip/hip_runtime.h>
+#include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <type_traits>
 #include <chrono>
 #include <cmath>
@@ -5246,6 +5249,7 @@ struct Tune {
     int handoff_index_limit = 0;     // tests: finish hand-offs of >= this many k-mers take u64 arena
                                      //   indices (0: 2^32, where they are needed)
     int handoff_max_chunk = 0;       // tests: cap on the hand-off's chunk size (0: memory-planned)
+    int final_kmers_piece_kb = 0;    // tests: skm_build_write_final_kmers' pinned piece size, KB (0: 64 MB)
 };
 
 }  // namespace skm
@@ -7809,6 +7813,7 @@ int skm_build_set_option(skm_build* b, const char* name, int64_t value) {
                : n == "emit_group" ? &t.emit_group
                : n == "handoff_index_limit" ? &t.handoff_index_limit
                : n == "handoff_max_chunk" ? &t.handoff_max_chunk
+               : n == "final_kmers_piece_kb" ? &t.final_kmers_piece_kb
                : n == "route_first_min" ? &t.route_first_min : nullptr;
         SKM_CHECK(f != nullptr, SKM_E_ARG, "unknown build option: " + n);
         SKM_CHECK(value >= 0 && value <= 0x7FFFFFFF, SKM_E_ARG, "option value out of range");
@@ -7818,6 +7823,8 @@ int skm_build_set_option(skm_build* b, const char* name, int64_t value) {
         if (n == "emit_group")
             SKM_CHECK(value == 0 || value == 1 || value == 2 || value == 4 || value == 8 || value == 16, SKM_E_ARG,
                       "emit_group must be 0, 1, 2, 4, 8 or 16");
+        if (n == "final_kmers_piece_kb")
+            SKM_CHECK(value <= (1 << 20), SKM_E_ARG, "final_kmers_piece_kb in [0, 2^20] (0 = 64 MB)");
         *f = (int)value;
     }
     b->prepared = false;  // pass geometry and buffers are re-planned on the next prepare/run
@@ -8039,6 +8046,42 @@ int skm_build_last_timings(skm_build* b, float* ms, int cap) {
     return n;
 }
 
+// KmerStatistics of the last run into *out (everything but keys, data and n), as skm_build_finish
+// and skm_build_stats return them; total = the kept k-mers of every rank
+static void finish_statistics(skm_build* b, skm_kept* out, uint64_t total) {
+    const uint32_t F = b->opts.n_functions;
+    out->distinct_functions = (uint32_t*)std::malloc(sizeof(uint32_t) * std::max<uint32_t>(F, 1));
+    out->seqs_with_func = (uint32_t*)std::malloc(sizeof(uint32_t) * std::max<uint32_t>(F, 1));
+    SKM_CHECK(out->distinct_functions && out->seqs_with_func, SKM_E_OOM, "host allocation failed");
+    if (F) {
+        SKM_HIP(hipMemcpyAsync(out->distinct_functions, b->d_dfunc.p, sizeof(uint32_t) * F, hipMemcpyDeviceToHost, b->stream));
+        SKM_HIP(hipMemcpyAsync(out->seqs_with_func, b->d_swf.p, sizeof(uint32_t) * F, hipMemcpyDeviceToHost, b->stream));
+    }
+    unsigned long long ctr[3];
+    SKM_HIP(hipMemcpyAsync(ctr, b->d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, b->stream));
+    const bool strict = b->world > 1 ? b->g_strict : b->seqid_strict;
+    std::vector<uint8_t> flags;
+    if (!strict) {
+        flags.resize(b->n_total);
+        if (b->n_total) SKM_HIP(hipMemcpyAsync(flags.data(), b->d_flags.p, b->n_total, hipMemcpyDeviceToHost, b->stream));
+    }
+    SKM_HIP(hipStreamSynchronize(b->stream));
+    out->n_functions = F;
+    out->distinct_signatures = total;
+    if (strict) {
+        out->n_seqs_with_signature = ctr[2];
+    } else {  // colliding seq ids (files with > max_seqs_per_file sequences): count distinct ids
+        const std::vector<uint32_t>& sid = b->world > 1 ? b->g_seqid : b->h_seqid;
+        std::vector<uint32_t> ids;
+        for (uint32_t s = 0; s < b->n_total; ++s)
+            if (flags[s]) ids.push_back(sid[s]);
+        std::sort(ids.begin(), ids.end());
+        out->n_seqs_with_signature = (uint64_t)(std::unique(ids.begin(), ids.end()) - ids.begin());
+    }
+    out->n_windows = b->n_windows;
+    out->n_records = b->n_local;
+}
+
 int skm_build_finish(skm_build* b, skm_kept* out) {
     SKM_API_BEGIN
     SKM_CHECK(b && out, SKM_E_ARG, "null argument");
@@ -8049,7 +8092,6 @@ int skm_build_finish(skm_build* b, skm_kept* out) {
     for (auto* x : bs) need |= !x->prepared || !x->ran;
     if (need) run_ranks(bs);
     std::memset(out, 0, sizeof(*out));
-    const uint32_t F = b->opts.n_functions;
     // kept k-mers: rank 0 gathers every rank's owned k-mers; other ranks return their own
     std::vector<uint64_t> mine;
     for (auto* x : bs) mine.push_back(x->n_kept);
@@ -8117,41 +8159,55 @@ int skm_build_finish(skm_build* b, skm_kept* out) {
             src_d = gd.as<skm_stored_kmer_data>();
         }
     }
-    out->distinct_functions = (uint32_t*)std::malloc(sizeof(uint32_t) * std::max<uint32_t>(F, 1));
-    out->seqs_with_func = (uint32_t*)std::malloc(sizeof(uint32_t) * std::max<uint32_t>(F, 1));
-    SKM_CHECK(out->distinct_functions && out->seqs_with_func, SKM_E_OOM, "host allocation failed");
-    if (F) {
-        SKM_HIP(hipMemcpyAsync(out->distinct_functions, b->d_dfunc.p, sizeof(uint32_t) * F, hipMemcpyDeviceToHost, b->stream));
-        SKM_HIP(hipMemcpyAsync(out->seqs_with_func, b->d_swf.p, sizeof(uint32_t) * F, hipMemcpyDeviceToHost, b->stream));
-    }
-    unsigned long long ctr[3];
-    SKM_HIP(hipMemcpyAsync(ctr, b->d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, b->stream));
-    const bool strict = b->world > 1 ? b->g_strict : b->seqid_strict;
-    std::vector<uint8_t> flags;
-    if (!strict) {
-        flags.resize(b->n_total);
-        if (b->n_total) SKM_HIP(hipMemcpyAsync(flags.data(), b->d_flags.p, b->n_total, hipMemcpyDeviceToHost, b->stream));
-    }
-    SKM_HIP(hipStreamSynchronize(b->stream));
+    finish_statistics(b, out, total);
     // keys ascending: device radix sort in chunks, streamed to the host arrays (skm_output.hip)
     if (!b->pool) b->pool.reset(new HostPool(HostPool::default_threads()));
     kept_handoff(src_k, src_d, n, b->stream, b->pool.get(), &out->keys, &out->data, &b->handoff,
                  (uint64_t)b->tune.handoff_index_limit, (uint64_t)b->tune.handoff_max_chunk);
     out->n = n;
-    out->n_functions = F;
-    out->distinct_signatures = total;
-    if (strict) {
-        out->n_seqs_with_signature = ctr[2];
-    } else {  // colliding seq ids (files with > max_seqs_per_file sequences): count distinct ids
-        const std::vector<uint32_t>& sid = b->world > 1 ? b->g_seqid : b->h_seqid;
-        std::vector<uint32_t> ids;
-        for (uint32_t s = 0; s < b->n_total; ++s)
-            if (flags[s]) ids.push_back(sid[s]);
-        std::sort(ids.begin(), ids.end());
-        out->n_seqs_with_signature = (uint64_t)(std::unique(ids.begin(), ids.end()) - ids.begin());
-    }
-    out->n_windows = b->n_windows;
-    out->n_records = b->n_local;
+    SKM_API_END
+}
+
+int skm_build_stats(skm_build* b, skm_kept* out) {
+    SKM_API_BEGIN
+    SKM_CHECK(b && out, SKM_E_ARG, "null argument");
+    SKM_CHECK(b->world == 1, SKM_E_STATE,
+              "skm_build_stats needs world_size 1: the statistics of a multi-rank build come with skm_build_finish");
+    SKM_HIP(hipSetDevice(b->device));
+    if (!b->prepared || !b->ran) run_ranks(Ranks{b});
+    std::memset(out, 0, sizeof(*out));
+    finish_statistics(b, out, b->n_kept);
+    out->n = b->n_kept;
+    SKM_API_END
+}
+
+int skm_build_write_final_kmers(skm_build* b, const char* path, skm_final_kmers_stats* stats) {
+    SKM_API_BEGIN
+    SKM_CHECK(b && path, SKM_E_ARG, "null argument");
+    SKM_CHECK(b->world == 1, SKM_E_STATE,
+              "skm_build_write_final_kmers needs world_size 1: the kept set of a multi-rank build is sharded over the "
+              "ranks");
+    struct Fd {  // closed on every way out; close() reports the one explicit close
+        int fd = -1;
+        ~Fd() {
+            if (fd >= 0) (void)::close(fd);
+        }
+        int close() {
+            const int r = ::close(fd);
+            fd = -1;
+            return r;
+        }
+    } f;
+    f.fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+    SKM_CHECK(f.fd >= 0, SKM_E_IO, std::string("cannot write ") + path + ": " + std::strerror(errno));
+    SKM_HIP(hipSetDevice(b->device));
+    if (!b->prepared || !b->ran) run_ranks(Ranks{b});
+    if (!b->pool) b->pool.reset(new HostPool(HostPool::default_threads()));
+    SKM_HIP(hipStreamSynchronize(b->stream));  // nothing of the run in flight
+    final_kmers_write(b->d_keys.as<uint64_t>(), b->d_data.as<skm_stored_kmer_data>(), b->n_kept, b->stream,
+                      b->pool.get(), f.fd, path, stats, (uint64_t)b->tune.handoff_index_limit,
+                      (uint64_t)b->tune.handoff_max_chunk, (uint64_t)b->tune.final_kmers_piece_kb << 10);
+    SKM_CHECK(f.close() == 0, SKM_E_IO, std::string("cannot write ") + path + ": " + std::strerror(errno));
     SKM_API_END
 }
 

@@ -1,4 +1,5 @@
-// skm_output.h -- the kept-set hand-off from HBM to host arrays in key order (skm_output.hip).
+// skm_output.h -- the kept-set hand-off from HBM to host arrays in key order, and final.kmers
+// written from the same arena (skm_output.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,5 +31,14 @@ struct HandoffStats {
 void kept_handoff(const uint64_t* dkeys, const skm_stored_kmer_data* ddata, uint64_t n, hipStream_t st,
                   HostPool* pool, uint64_t** keys_out, skm_stored_kmer_data** data_out, HandoffStats* stats,
                   uint64_t index_limit = 0, uint64_t max_chunk = 0);
+
+// final.kmers from the same arena, formatted on the device (skm_build_write_final_kmers): the
+// hand-off's chunks (histogram, plan, select, sort), then per chunk k_fk_len + a scan of the tile
+// sizes + k_fk_emit into one of two text buffers, whose bytes leave through two pinned pieces of
+// piece_bytes (0 = 64 MB) and are written to fd at their file offsets.  A failed write throws
+// SKM_E_IO naming `path`.  index_limit / max_chunk as above.
+void final_kmers_write(const uint64_t* dkeys, const skm_stored_kmer_data* ddata, uint64_t n, hipStream_t st,
+                       HostPool* pool, int fd, const char* path, skm_final_kmers_stats* stats, uint64_t index_limit,
+                       uint64_t max_chunk, uint64_t piece_bytes);
 
 }  // namespace skm

@@ -14,7 +14,11 @@
 // stop before touching the GPU; used by the CPU tests), --mph-seed N, --recall-db host|device (the
 // recall DB from the downloaded kept k-mers, or built on the GPU from the resident ones),
 // --perfect-hash-source host|device (likewise for kmer_data.mph / .dat: skm_build_mph_db; the files
-// are the same).
+// are the same), --final-kmers-source host|device (final.kmers formatted by the host threads from
+// the downloaded kept k-mers, or sorted, formatted and streamed out by the GPU from the resident
+// ones: skm_build_write_final_kmers; the file is the same).  With all three on `device` (or no
+// --perfect-hash) the kept set never comes to the host: skm_build_finish is not called, the three
+// stdout lines and distinct_functions come from skm_build_stats.
 // Multi-GPU: --n-gpus N forks one process per GPU (rank r on device r) before
 // any GPU or thread use; or, under an external launcher (RANK / WORLD_SIZE / LOCAL_RANK in the
 // environment, e.g. torchrun --no-python), each launched process is one rank and rank 0 hands the
@@ -179,7 +183,8 @@ int main(int argc, char** argv) {
                 {"dump-extract", 0, false, false},     {"mph-seed", 0, false, false},
                 {"n-gpus", 0, false, false},           {"comm", 0, false, false},
                 {"comm-file", 0, false, false},        {"recall-db", 0, false, false},
-                {"perfect-hash-source", 0, false, false}, {"best-call", 0, false, false}};
+                {"perfect-hash-source", 0, false, false}, {"best-call", 0, false, false},
+                {"final-kmers-source", 0, false, false}};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
     if (op.has("help")) {
@@ -206,6 +211,11 @@ int main(int argc, char** argv) {
                   << "  --perfect-hash-source arg            host (default): the perfect hash from the downloaded kept k-mers;\n"
                   << "                                       device: hash and data files written from the DB built on the GPU\n"
                   << "                                       from the build's resident kept k-mers (needs --perfect-hash, one GPU)\n"
+                  << "  --final-kmers-source arg             host (default): final.kmers formatted on the host from the downloaded\n"
+                  << "                                       kept k-mers; device: sorted, formatted and streamed out by the GPU from\n"
+                  << "                                       the build's resident kept k-mers (needs --final-kmers, one GPU); with\n"
+                  << "                                       --recall-db device and --perfect-hash-source device (or no\n"
+                  << "                                       --perfect-hash) the kept k-mers are never copied to the host\n"
                   << "  --best-call arg                      host (default) | device: where the recall pass runs find_best_call\n"
                   << "  -h [ --help ]                        show this help message\n";
         return 1;
@@ -230,6 +240,15 @@ int main(int argc, char** argv) {
         die("--perfect-hash-source device needs --perfect-hash: it names the file the hash is written to");
     if (ph_source == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
         die("--perfect-hash-source device needs one GPU: the kept k-mers of a multi-rank build are sharded over the ranks");
+    const std::string fk_source = op.get("final-kmers-source", "host");
+    if (fk_source != "host" && fk_source != "device") die("--final-kmers-source must be host or device");
+    if (fk_source == "device" && op.get("final-kmers").empty())
+        die("--final-kmers-source device needs --final-kmers: it names the file the k-mers are written to");
+    if (fk_source == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
+        die("--final-kmers-source device needs one GPU: the kept k-mers of a multi-rank build are sharded over the ranks");
+    // every consumer of the kept set on the device: no host copy of it is made
+    const bool kept_on_device = fk_source == "device" && recall_db == "device" &&
+                                (ph_source == "device" || op.get("perfect-hash").empty());
     int local_rank = 0;
     if (launched) {
         if (comm == "host") die("--comm host needs --n-gpus (forked ranks)");
@@ -454,7 +473,11 @@ int main(int argc, char** argv) {
     const double t_run = now_s() - t0;
     t0 = now_s();
     skm_kept kept{};
-    check(skm_build_finish(b, &kept), "skm_build_finish");
+    if (kept_on_device)
+        check(skm_build_stats(b, &kept), "skm_build_stats");
+    else
+        check(skm_build_finish(b, &kept), "skm_build_finish");
+    const uint64_t kept_host_bytes = kept.keys ? (8 + sizeof(skm_stored_kmer_data)) * kept.n : 0;
     const double t_finish = now_s() - t0;
     float ph[12] = {0};
     int nph = skm_build_last_timings(b, ph, 12);
@@ -485,7 +508,11 @@ int main(int argc, char** argv) {
         ko.release_work = 1;
         check(skm_build_kept_db(b, &ko, &kdb), "skm_build_kept_db");
     }
-    skm_build_destroy(b);
+    // --final-kmers-source device: the handle lives until the final.kmers thread has written the file
+    if (fk_source != "device") {
+        skm_build_destroy(b);
+        b = nullptr;
+    }
     if (rank != 0) {  // rank 0 holds every kept k-mer and the all-reduced statistics
         skm_kept_free(&kept);
         return 0;
@@ -504,7 +531,10 @@ int main(int argc, char** argv) {
         final_kmers_thread = std::thread([&]() {
             const double tk = now_s();
             std::cerr << "writing kmers to " << quoted(final_kmers) << "\n";
-            write_final_kmers(final_kmers, kept, std::max(1, n_threads / 2));
+            if (fk_source == "device")  // from here on this thread alone touches the build handle
+                check(skm_build_write_final_kmers(b, final_kmers.c_str(), nullptr), "skm_build_write_final_kmers");
+            else
+                write_final_kmers(final_kmers, kept, std::max(1, n_threads / 2));
             t_final_kmers = now_s() - tk;
             std::cerr << "writing kmers to " << quoted(final_kmers) << " complete\n";
         });
@@ -593,6 +623,7 @@ int main(int argc, char** argv) {
         std::cerr << "Awaiting completion of final kmers dump\n";
         final_kmers_thread.join();
     }
+    skm_build_destroy(b);
     skm_kept_free(&kept);
     if (!mesh.wait_children(err)) die(err);
     std::cerr << "timing: parse " << t_parse << " s, build " << t_build << " s (device pipeline "
@@ -602,7 +633,8 @@ int main(int argc, char** argv) {
               << " finish " << t_finish << " final_kmers " << t_final_kmers << " mph " << t_mph << " recall "
               << t_recall << " recall_device " << t_recall_dev << " total " << now_s() - t_start << " startup "
               << t_startup << " defs " << t_defs << " hip_init " << t_hip_init << " create " << t_create
-              << " parse_files " << t_files << " fm_load " << t_fm << " recall_deferred " << recall_deferred << "\n";
+              << " parse_files " << t_files << " fm_load " << t_fm << " recall_deferred " << recall_deferred
+              << " kept_host_bytes " << kept_host_bytes << "\n";
     std::cerr << "all done\n";
     fast_exit(0);  // every output file is closed by now
 }
