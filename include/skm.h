@@ -278,6 +278,11 @@ int skm_build_debug_overflow(skm_build* b, uint32_t* out, int cap);
  * their span (nwg, span), pass_bits, owner_bits, b1_bits.  The five key-range-pass values
  * (sel_wg .. pf_nwg) are 0 after a one-pass run.  Returns 11, SKM_E_STATE without a completed run. */
 int skm_build_debug_front(skm_build* b, uint64_t* out, int cap);
+/* Diagnostics (read-only, after a run with key-range passes): the staging's exact starts of `pass`,
+ * a pass of the run's last emission group: (pf_nwg + 1) rows of 64, row w column d = where staging
+ * workgroup w begins in level-0 slice d, row pf_nwg = the slices' ends (at most cap written);
+ * returns the value count.  SKM_E_ARG for a pass of an earlier group, SKM_E_STATE after one pass. */
+int skm_build_debug_stage_starts(skm_build* b, uint32_t pass, uint64_t* out, int cap);
 /* Diagnostics (read-only, after a run): this rank's window count of every key-range pass of the
  * last run, after any heavy-key routing (at most cap written); returns the pass count.  With one
  * pass: the single valid window count. */

@@ -141,6 +141,7 @@ _SIGS = {
     "skm_build_debug_jobs": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_int]),
     "skm_build_debug_overflow": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_int]),
     "skm_build_debug_front": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
+    "skm_build_debug_stage_starts": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64), C.c_int]),
     "skm_build_debug_pass_windows": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     "skm_debug_chain_bench": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_float)]),
     "skm_debug_chain_eval": (C.c_int, [_P, C.c_uint32, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -457,6 +458,17 @@ class SignatureBuilder:
         _check(min(n, 0))
         assert n == len(names), n
         return {names[i]: int(v[i]) for i in range(n)}
+
+    def debug_stage_starts(self, pass_id: int) -> np.ndarray:
+        """skm_build_debug_stage_starts: the (pf_nwg + 1) x 64 table of exact staging starts of a
+        key-range pass of the last run's last emission group (row w, column d: where staging
+        workgroup w begins in level-0 slice d; the last row: the slices' ends)."""
+        rows = self.debug_front()["pf_nwg"] + 1
+        out = np.zeros(rows * 64, dtype=np.uint64)
+        n = lib().skm_build_debug_stage_starts(self._h, pass_id, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size)
+        _check(min(n, 0))
+        assert n == out.size, (n, out.size)
+        return out.reshape(rows, 64)
 
     def debug_pass_windows(self) -> list:
         """skm_build_debug_pass_windows: this rank's windows of every key-range pass of the last run

@@ -2009,30 +2009,59 @@ __global__ __launch_bounds__(EMIT_THREADS) void k_pass_emit(const uint8_t* __res
 }
 
 // The level-1 histogram of each pass of a group from its entries' bucket bits: blockIdx.y = the
-// pass within the group, blockIdx.x strides over its list; NB counters in LDS, merged once.
+// pass within the group, blockIdx.x strides over the pass's staging spans (span w = the entries
+// [w * span, (w + 1) * span) that workgroup w of k_extract_stage_pos stages); NB counters in LDS,
+// merged once.  At each span's end the 64 level-0 group sums of the bins, less their values at the
+// previous span's end, are the span's element count per level-0 destination: row w of cnt0[q]
+// (nwg rows of 64; zero rows past the pass's end), from which k_pass_starts gives every staging
+// workgroup its exact range of every level-0 slice.  No second LDS atomic per element.
 constexpr uint32_t PH_THREADS = 512;
+constexpr int SC_L0_BITS = 6;  // the staged scatter's pass-1 fan-out (below)
 __global__ __launch_bounds__(PH_THREADS) void k_pass_hist(const uint64_t* __restrict__ pos, uint64_t cap,
                                                           const unsigned long long* __restrict__ npos, uint32_t NB,
-                                                          int rem_bits, uint32_t* __restrict__ hist) {
+                                                          int rem_bits, uint32_t* __restrict__ hist, uint64_t span,
+                                                          uint32_t nwg, int l0_shift, uint32_t* __restrict__ cnt0) {
     extern __shared__ uint32_t s_h[];  // [NB]
+    __shared__ uint32_t s_prev[1 << SC_L0_BITS];
     const uint32_t q = blockIdx.y;
     for (uint32_t k = threadIdx.x; k < NB; k += PH_THREADS) s_h[k] = 0;
+    if (threadIdx.x < (1u << SC_L0_BITS)) s_prev[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t n = min((uint64_t)npos[q], cap);
     const uint64_t* p = pos + (uint64_t)q * cap;
+    uint32_t* cq = cnt0 + (uint64_t)q * nwg * (1u << SC_L0_BITS);
     constexpr uint32_t U = 4;
-    for (uint64_t j0 = (uint64_t)blockIdx.x * PH_THREADS * U; j0 < n; j0 += (uint64_t)gridDim.x * PH_THREADS * U) {
-        uint64_t v[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; ++u) {
-            const uint64_t j = j0 + u * PH_THREADS + threadIdx.x;
-            v[u] = j < n ? p[j] : ~0ull;
+    constexpr uint32_t GT = PH_THREADS >> SC_L0_BITS;  // threads per level-0 group (8, a power of two)
+    const uint32_t gsz = 1u << l0_shift, gd = threadIdx.x / GT, gs = threadIdx.x % GT;
+    for (uint32_t w = blockIdx.x; w < nwg; w += gridDim.x) {
+        const uint64_t a = (uint64_t)w * span, e = min(a + span, n);
+        if (a >= n) {  // uniform: a span past the pass's end
+            if (threadIdx.x < (1u << SC_L0_BITS)) cq[(uint64_t)w * (1u << SC_L0_BITS) + threadIdx.x] = 0;
+            continue;
         }
+        for (uint64_t j0 = a; j0 < e; j0 += PH_THREADS * U) {
+            uint64_t v[U];
 #pragma unroll
-        for (uint32_t u = 0; u < U; ++u)
-            if (v[u] != ~0ull) atomicAdd(&s_h[(uint32_t)((v[u] & H43_MASK) >> rem_bits) & (NB - 1)], 1u);
+            for (uint32_t u = 0; u < U; ++u) {
+                const uint64_t j = j0 + u * PH_THREADS + threadIdx.x;
+                v[u] = j < e ? p[j] : ~0ull;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u)
+                if (v[u] != ~0ull) atomicAdd(&s_h[(uint32_t)((v[u] & H43_MASK) >> rem_bits) & (NB - 1)], 1u);
+        }
+        __syncthreads();
+        uint32_t sum = 0;
+        for (uint32_t k = gs; k < gsz; k += GT) sum += s_h[gd * gsz + k];
+        sum += xshfl<1>(sum);
+        sum += xshfl<2>(sum);
+        sum += xshfl<4>(sum);
+        if (gs == 0) {
+            cq[(uint64_t)w * (1u << SC_L0_BITS) + gd] = sum - s_prev[gd];
+            s_prev[gd] = sum;
+        }
+        __syncthreads();  // the next span's atomics follow the group sums
     }
-    __syncthreads();
     uint32_t* hq = hist + (uint64_t)q * NB;
     for (uint32_t k = threadIdx.x; k < NB; k += PH_THREADS)
         if (s_h[k]) atomicAdd(&hq[k], s_h[k]);
@@ -2090,13 +2119,13 @@ __global__ __launch_bounds__(EX_THREADS) void k_extract(ExtractArgs X) {
 // ~4x write amplification measured).  Pass 1 partitions by the top 6 bucket bits (64-way) as
 // the windows are extracted; pass 2 splits each of those ranges by the remaining bits.  Each
 // pass stages 4096 elements per round in LDS, sorted by destination, reserves one global range
-// per destination per round with one atomic, and writes runs of ~64 / ~32 contiguous elements.
+// per destination per round with one atomic, and writes runs of ~64 / ~32 contiguous elements
+// (with key-range passes pass 1 reserves nothing: its workgroups own exact ranges, k_pass_starts).
 // Element order inside a bucket is immaterial (elements carry their ordinal).  Between the
 // passes the low 16 bits of lo hold the full bucket id instead of (len - i) mod 2^16, which
 // pass 2 restores from len mod 2^16 (hi[63:48]) and i.
 // ------------------------------------------------------------------------------------------
 constexpr int SC_ROUND = 4096;        // elements staged per round (64 KB of LDS)
-constexpr int SC_L0_BITS = 6;         // pass-1 fan-out
 constexpr int SC_POS = SC_ROUND / EX_THREADS;  // windows per thread per round (8)
 constexpr uint64_t SC_SLICE = 65536;  // pass-2 elements per workgroup
 
@@ -2261,17 +2290,31 @@ __global__ __launch_bounds__(EX_THREADS, 2) void k_extract_stage(ExtractArgs X, 
 // sel[0..nrows] (k_sel_scan): each thread's entries ascend, so it walks its row forward -- one
 // binary search per thread at the start, then a compare per entry.  Each position finds its
 // sequence through blk2seq, reusing the previous one while it still contains the window.
+// No global atomics: workgroup w owns [wstart[w][d], wstart[w + 1][d]) of every level-0 slice d
+// (k_pass_starts, from k_pass_hist's per-span counts), keeps its 64 running cursors in LDS and
+// appends each round's runs to them (k_extract_stage and the split reserve theirs from shared
+// cursors, stage_reserve: one returning device-scope add per destination per round, on 64 words
+// that every workgroup of the launch hits).  Nothing is stored outside the workgroup's ranges,
+// whatever the counts say, and cursors that do not end on the next row set RUN_F_CAP.
 template <int R, int MINB>
 __global__ __launch_bounds__(EX_THREADS, MINB) void k_extract_stage_pos(ExtractArgs X, const uint64_t* __restrict__ pos,
                                                                         const unsigned long long* __restrict__ np,
                                                                         const uint64_t* __restrict__ sel, uint32_t nrows,
                                                                         uint64_t sel_span,
-                                                                        unsigned long long* __restrict__ cur0,
+                                                                        const uint32_t* __restrict__ wstart,
+                                                                        unsigned long long* __restrict__ run,
                                                                         uint64_t* __restrict__ out_hi,
                                                                         uint64_t* __restrict__ out_lo) {
     constexpr int SC_POS = R / EX_THREADS;
+    constexpr uint32_t N0 = 1u << SC_L0_BITS;
     const uint64_t n = min((uint64_t)*np, X.pos_cap);
     __shared__ StageLdsT<R> L;
+    __shared__ uint64_t s_cur[N0];  // the running cursors (64 bits: wrong counts cannot wrap one below its start)
+    __shared__ uint32_t s_end[N0];  // the ranges' ends
+    if (threadIdx.x < N0) {  // next read behind the first round's barriers, by this thread alone (s_cur)
+        s_cur[threadIdx.x] = wstart[(uint64_t)blockIdx.x * N0 + threadIdx.x];
+        s_end[threadIdx.x] = wstart[(uint64_t)(blockIdx.x + 1) * N0 + threadIdx.x];
+    }
     const int nbits = X.owner_bits + X.b1_bits;
     const uint32_t NB = 1u << nbits;
     const int rem_bits = KEY_BITS - X.pass_bits - nbits;
@@ -2302,9 +2345,16 @@ __global__ __launch_bounds__(EX_THREADS, MINB) void k_extract_stage_pos(ExtractA
         const uint64_t j = begin + (uint64_t)threadIdx.x * SC_POS + t;
         nxt[t] = j < end ? pos[j] : ~0ull;
     }
+    // Three barriers a round (k_extract_stage: eight).  The 64 destinations are the lanes of wave 0,
+    // which scans their counts alone, zeroes them for the next round and takes the bases from its
+    // cursors; a wave that has written its share of a round goes on to rank the next round's
+    // elements (L.cnt only) and meets the others at that round's first barrier, which thereby also
+    // ends the write loop for wave 0's next L.off / L.base.  There is no barrier after the write loop,
+    // so between the top of a round and its first barrier nothing but agg_rank may touch LDS, and that
+    // only L.cnt: do not add LDS writes (or reads of L.off / L.base / L.hi / L.lo / L.dst) above it.
+    if (threadIdx.x < N0) L.cnt[threadIdx.x] = 0;
+    __syncthreads();
     for (uint64_t base = begin; base < end; base += R) {
-        if (threadIdx.x < 128) L.cnt[threadIdx.x] = 0;
-        __syncthreads();
         uint64_t ent[SC_POS];
 #pragma unroll
         for (int t = 0; t < SC_POS; ++t) ent[t] = nxt[t];
@@ -2340,7 +2390,21 @@ __global__ __launch_bounds__(EX_THREADS, MINB) void k_extract_stage_pos(ExtractA
 #pragma unroll
         for (int t = 0; t < SC_POS; ++t) rk[t] = agg_rank(L.cnt, l0[t], ent[t] != ~0ull);
         __syncthreads();
-        const uint32_t tot = stage_reserve(L, 1u << SC_L0_BITS, cur0, 0);
+        // stage_reserve's offsets (wave 0 alone: one lane per destination); a round's base is the
+        // workgroup's own cursor, packed with how many of the round's elements still fit its range
+        if (threadIdx.x < N0) {
+            const uint32_t c = L.cnt[threadIdx.x];
+            L.cnt[threadIdx.x] = 0;
+            const uint32_t inc = wave_incl_scan(c);
+            L.off[threadIdx.x] = inc - c;
+            if (threadIdx.x == N0 - 1) L.off[N0] = inc;
+            const uint64_t cur = s_cur[threadIdx.x], e = s_end[threadIdx.x];
+            const uint64_t fit = cur < e ? min((uint64_t)c, e - cur) : 0ull;  // c unless the counts are wrong
+            L.base[threadIdx.x] = (cur & 0xFFFFFFFFull) | (fit << 32);
+            s_cur[threadIdx.x] = cur + c;
+        }
+        __syncthreads();
+        const uint32_t tot = L.off[N0];
 #pragma unroll
         for (int t = 0; t < SC_POS; ++t)
             if (ent[t] != ~0ull) {
@@ -2352,12 +2416,18 @@ __global__ __launch_bounds__(EX_THREADS, MINB) void k_extract_stage_pos(ExtractA
         __syncthreads();
         for (uint32_t j = threadIdx.x; j < tot; j += blockDim.x) {
             const uint32_t d = L.dst[j];
-            const uint64_t o = L.base[d] + (j - L.off[d]);
-            out_hi[o] = L.hi[j];
-            out_lo[o] = L.lo[j];
+            const uint64_t bf = L.base[d];
+            const uint32_t r = j - L.off[d];
+            if (r < (uint32_t)(bf >> 32)) {  // inside [wstart[w][d], wstart[w + 1][d])
+                const uint64_t o = (bf & 0xFFFFFFFFull) + r;
+                out_hi[o] = L.hi[j];
+                out_lo[o] = L.lo[j];
+            }
         }
-        __syncthreads();
+        // no barrier here: the next round's first one ends this loop (see above the round loop)
     }
+    if (threadIdx.x < N0 && s_cur[threadIdx.x] != s_end[threadIdx.x])  // its own cursor
+        atomicOr(&run[RUN_FLAGS], (unsigned long long)RUN_F_CAP);
 }
 
 // cur0[b0] = start of pass-1 range b0; cur1[b] = start of bucket b; slice prefix for pass 2
@@ -3485,20 +3555,29 @@ __global__ __launch_bounds__(1024) void k_part_order(const uint64_t* __restrict_
 // pass (the five scan kernels and k_part_order did, each behind the previous pass's tail grids).
 // With one histogram row the column sums and offsets of the one-pass path are the row itself:
 //   bstart[NB + 1]  absolute bucket starts (the owners' ranges in order) and the pass's element count
-//   cur1 / cur0     the split's and the staging's cursors (k_stage_init), slice_base the split's slices
+//   cur1 / cur0     the split's cursors and the level-0 slice starts (k_stage_init), slice_base the
+//                   split's slices
 //   order[NB + 1]   k_part_order's list and its nbig (one rank only: after an exchange the partition
 //                   orders the received layout)
+//   wstart[(nwg + 1) * 64]  the staging's exact starts: the column scan of k_pass_hist's span counts
+//                   cnt0 over the level-0 slice starts (k_extract_stage_pos reserves nothing; cur0
+//                   stays filled for the one-pass path's kernels)
 // Copy c of every output is blockIdx.x of set `set0` (PS_CUR0 / PS_SLICES words of cur0 / slice_base
-// per copy): a pass owns its copy, the staging's atomics consume the cursors.
+// per copy): a pass owns its copy, the split's atomics consume cur1 (nothing consumes cur0 here: the
+// staging of a key-range pass appends from wstart).
 constexpr uint32_t PS_CUR0 = (1u << SC_L0_BITS) * CUR_STRIDE, PS_SLICES = 80;
 
 __global__ __launch_bounds__(1024) void k_pass_starts(const uint32_t* __restrict__ histg, uint32_t NB, int l0_shift,
                                                       uint32_t set0, uint64_t* __restrict__ bstart,
                                                       unsigned long long* __restrict__ cur0,
                                                       unsigned long long* __restrict__ cur1,
-                                                      uint32_t* __restrict__ slice_base, uint32_t* __restrict__ order) {
+                                                      uint32_t* __restrict__ slice_base, uint32_t* __restrict__ order,
+                                                      const uint32_t* __restrict__ cnt0, uint32_t nwg,
+                                                      uint32_t* __restrict__ wstart) {
     __shared__ uint32_t s_wave[48];
     __shared__ uint32_t s_n[(1 << SC_L0_BITS) + 1];
+    __shared__ uint32_t s_start[1 << SC_L0_BITS];
+    __shared__ uint32_t s_part[16 << SC_L0_BITS];  // [row part][destination]
     const uint32_t c = set0 + blockIdx.x;
     const uint32_t* hist = histg + (uint64_t)blockIdx.x * NB;
     bstart += (uint64_t)c * (NB + 1);
@@ -3523,6 +3602,7 @@ __global__ __launch_bounds__(1024) void k_pass_starts(const uint32_t* __restrict
         const uint64_t a = bstart[(uint64_t)threadIdx.x << l0_shift];
         const uint64_t e = bstart[(uint64_t)(threadIdx.x + 1) << l0_shift];
         cur0[threadIdx.x * CUR_STRIDE] = a;
+        s_start[threadIdx.x] = (uint32_t)a;
         s_n[threadIdx.x] = (uint32_t)((e - a + SC_SLICE - 1) / SC_SLICE);
     }
     __syncthreads();
@@ -3533,6 +3613,27 @@ __global__ __launch_bounds__(1024) void k_pass_starts(const uint32_t* __restrict
             acc += s_n[b];
         }
         slice_base[n0] = acc;
+    }
+    // the staging's exact starts: wstart[w][d] = start(d) + the counts of the spans before w, row
+    // nwg the slice's end.  16 threads a column, each over a run of rows (a wave reads a row's 64
+    // counts in one line pair): the runs' sums, their prefix, then the rows.
+    {
+        cnt0 += (uint64_t)blockIdx.x * nwg * n0;
+        wstart += (uint64_t)c * (nwg + 1) * n0;
+        const uint32_t d = threadIdx.x & (n0 - 1), part = threadIdx.x >> SC_L0_BITS, parts = blockDim.x >> SC_L0_BITS;
+        const uint32_t per_w = (nwg + parts - 1) / parts;
+        const uint32_t w0 = min(nwg, part * per_w), w1 = min(nwg, w0 + per_w);
+        uint32_t sum = 0;
+        for (uint32_t w = w0; w < w1; ++w) sum += cnt0[(uint64_t)w * n0 + d];
+        s_part[part * n0 + d] = sum;
+        __syncthreads();
+        uint32_t at = s_start[d];
+        for (uint32_t k = 0; k < part; ++k) at += s_part[k * n0 + d];
+        for (uint32_t w = w0; w < w1; ++w) {
+            wstart[(uint64_t)w * n0 + d] = at;
+            at += cnt0[(uint64_t)w * n0 + d];
+        }
+        if (part == parts - 1) wstart[(uint64_t)nwg * n0 + d] = at;
     }
     if (!order) return;
     order += (uint64_t)c * (NB + 1);
@@ -5324,6 +5425,7 @@ struct skm_build {
     DevBuf d_stg_hi, d_stg_lo;
     DevBuf d_part_order;                // k_part_order's workgroup -> bucket map
     DevBuf d_cur0, d_cur1, d_slices;   // staged scatter cursors
+    DevBuf d_cnt0, d_wstart;           // key-range passes: per-span level-0 counts of a group, the passes' exact starts
     DevBuf d_flagbits;
     DevBuf d_keys, d_data, d_ctr, d_flags, d_dfunc, d_swf, d_ovf, d_ovf_hi, d_ovf_lo, d_ovf_heads, d_ovf_job, d_ovf_fm;
     DevBuf d_jobs, d_lens, d_stamps, d_big_desc, d_big_out;
@@ -6003,6 +6105,10 @@ void ensure_pass_copies(skm_build* b) {
     b->d_cur1.ensure(8ull * NB * CUR_STRIDE * nc);
     b->d_slices.ensure(4ull * PS_SLICES * nc);
     b->d_part_order.ensure(4ull * (NB + 1) * nc);
+    if (b->pass_bits) {  // the staging's exact starts, (pf_nwg + 1) rows of 64 per copy; one group's span counts
+        b->d_wstart.ensure(4ull * ((uint64_t)b->pf_nwg + 1) * (1u << SC_L0_BITS) * nc);
+        b->d_cnt0.ensure(4ull * b->pf_nwg * (1u << SC_L0_BITS) * b->emit_g);
+    }
 }
 
 // extract buffers (one pass of this shard), the pass-id bytes, and with passes the kept arena
@@ -6380,16 +6486,20 @@ void emit_group(skm_build* b, uint32_t g, hipStream_t st) {
     else
         SKM_EMIT(1);
 #undef SKM_EMIT
-    // the group's histograms from the entries' bucket bits (8 B per window read, no residues)
+    // the group's histograms from the entries' bucket bits (8 B per window read, no residues), and
+    // each staging span's count per level-0 destination (the spans of this run's staging launches)
+    const int l0_shift = b->owner_bits + b->b1_bits - SC_L0_BITS;
     SKM_HIP(hipMemsetAsync(b->d_histg.p, 0, sizeof(uint32_t) * NB * G, st));
     SKM_LAUNCH(b, k_pass_hist, dim3(256, G), dim3(PH_THREADS), 4u * NB, st, b->d_posg.as<uint64_t>(), cap,
-               b->d_npos.as<unsigned long long>() + (uint64_t)g * G, NB, rem_bits, b->d_histg.as<uint32_t>());
-    // every pass's bucket starts, cursors, slices and partition order from its histogram row, into
-    // the pass's copies of this group's set
-    SKM_LAUNCH(b, k_pass_starts, dim3(G), dim3(1024), 0, st, b->d_histg.as<uint32_t>(), NB,
-               b->owner_bits + b->b1_bits - SC_L0_BITS, (g & 1u) * G, b->d_bstart.as<uint64_t>(),
-               b->d_cur0.as<unsigned long long>(), b->d_cur1.as<unsigned long long>(), b->d_slices.as<uint32_t>(),
-               b->world == 1 && b->tune.part_order ? b->d_part_order.as<uint32_t>() : nullptr);
+               b->d_npos.as<unsigned long long>() + (uint64_t)g * G, NB, rem_bits, b->d_histg.as<uint32_t>(),
+               b->pf_span, b->pf_nwg, l0_shift, b->d_cnt0.as<uint32_t>());
+    // every pass's bucket starts, cursors, slices, partition order and exact staging starts from its
+    // histogram row and span counts, into the pass's copies of this group's set
+    SKM_LAUNCH(b, k_pass_starts, dim3(G), dim3(1024), 0, st, b->d_histg.as<uint32_t>(), NB, l0_shift, (g & 1u) * G,
+               b->d_bstart.as<uint64_t>(), b->d_cur0.as<unsigned long long>(), b->d_cur1.as<unsigned long long>(),
+               b->d_slices.as<uint32_t>(),
+               b->world == 1 && b->tune.part_order ? b->d_part_order.as<uint32_t>() : nullptr,
+               b->d_cnt0.as<uint32_t>(), b->pf_nwg, b->d_wstart.as<uint32_t>());
     SKM_HIP(hipGetLastError());
     if (st != b->stream) SKM_HIP(hipEventRecord(b->ev_emit, st));
 }
@@ -6475,6 +6585,9 @@ void phase_extract(skm_build* b, uint32_t pass) {
     unsigned long long* cur0 = b->d_cur0.as<unsigned long long>() + (uint64_t)pc * PS_CUR0;
     unsigned long long* cur1 = b->d_cur1.as<unsigned long long>() + (uint64_t)pc * NB * CUR_STRIDE;
     uint32_t* slices = b->d_slices.as<uint32_t>() + (uint64_t)pc * PS_SLICES;
+    // key-range passes: the staging workgroups' exact starts (k_pass_starts), nothing reserved at run time
+    const uint32_t* wstart =
+        b->pass_bits ? b->d_wstart.as<uint32_t>() + (uint64_t)pc * (((uint64_t)b->pf_nwg + 1) << SC_L0_BITS) : nullptr;
     if (!b->pass_bits) {
         const uint32_t nrb = (uint32_t)ceil_div(hist_rows, SCAN_ROWS);
         dim3 gsc((NB + 255) / 256, nrb);
@@ -6506,13 +6619,13 @@ void phase_extract(skm_build* b, uint32_t pass) {
                    b->d_posg.as<uint64_t>() + (uint64_t)(pass % b->emit_g) * std::max<uint64_t>(b->pass_max, 1),
                    b->d_npos.as<unsigned long long>() + pass,
                    b->d_seloff.as<uint64_t>() + (uint64_t)pass * (b->sel_wg + 1), b->sel_wg, b->sel_span,
-                   cur0, stg_hi, stg_lo);
+                   wstart, b->d_run.as<unsigned long long>(), stg_hi, stg_lo);
     else if (b->pass_bits)
         SKM_LAUNCH_AS(b, "k_extract_stage_pos", (k_extract_stage_pos<SC_ROUND, 2>), dim3(nwg), dim3(EX_THREADS), 0, st, X,
                    b->d_posg.as<uint64_t>() + (uint64_t)(pass % b->emit_g) * std::max<uint64_t>(b->pass_max, 1),
                    b->d_npos.as<unsigned long long>() + pass,
                    b->d_seloff.as<uint64_t>() + (uint64_t)pass * (b->sel_wg + 1), b->sel_wg, b->sel_span,
-                   cur0, stg_hi, stg_lo);
+                   wstart, b->d_run.as<unsigned long long>(), stg_hi, stg_lo);
     else
         SKM_LAUNCH(b, k_extract_stage, dim3(nwg), dim3(EX_THREADS), 0, st, X, cur0, stg_hi, stg_lo);
     // (the split overwrites recs, which only k_partition reads: the previous pass's tail reads its
@@ -7894,6 +8007,25 @@ int skm_build_debug_front(skm_build* b, uint64_t* out, int cap) {
     return 11;
 }
 
+// Diagnostics: the staging's exact starts of a key-range pass of the last run's LAST emission group
+// (k_pass_starts' wstart: row w, column d = where staging workgroup w begins in level-0 slice d; row
+// pf_nwg = the slices' ends; the earlier groups' copies are overwritten by then); returns the value
+// count, (pf_nwg + 1) * 64.
+int skm_build_debug_stage_starts(skm_build* b, uint32_t pass, uint64_t* out, int cap) {
+    if (!b || !out) return SKM_E_ARG;
+    if (!b->ran || !b->pass_bits || b->work_released || !b->d_wstart.p) return SKM_E_STATE;
+    const uint32_t P = 1u << b->pass_bits;
+    if (pass >= P || pass / b->emit_g != (P - 1) / b->emit_g) return SKM_E_ARG;
+    if (hipSetDevice(b->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return SKM_E_HIP;
+    const uint64_t n = ((uint64_t)b->pf_nwg + 1) << SC_L0_BITS;
+    std::vector<uint32_t> v(n);
+    if (hipMemcpy(v.data(), b->d_wstart.as<uint32_t>() + (uint64_t)pass_copy(b, pass) * n, 4 * n, hipMemcpyDeviceToHost) !=
+        hipSuccess)
+        return SKM_E_HIP;
+    for (uint64_t i = 0; i < n && i < (uint64_t)std::max(cap, 0); ++i) out[i] = v[i];
+    return (int)n;
+}
+
 // Diagnostics: the window count of every key-range pass of the last run (k_sel_scan's npos, after
 // any routing) -- this rank's windows, before the exchange; returns the pass count P.  With one pass
 // there is no position list: the one value is the valid window count of prepare's scan.
@@ -8293,7 +8425,8 @@ static void release_work(skm_build* b) {
     DevBuf* work[] = {
         &b->d_res, &b->d_meta, &b->d_blk2seq, &b->d_glen, &b->d_hist, &b->d_offs, &b->d_partial, &b->d_rbbase,
         &b->d_bstart32, &b->d_bstart, &b->d_owner_start, &b->d_recs_hi, &b->d_recs_lo, &b->d_tmp_hi, &b->d_tmp_lo,
-        &b->d_stg_hi, &b->d_stg_lo, &b->d_part_order, &b->d_cur0, &b->d_cur1, &b->d_slices, &b->d_flagbits,
+        &b->d_stg_hi, &b->d_stg_lo, &b->d_part_order, &b->d_cur0, &b->d_cur1, &b->d_slices, &b->d_cnt0, &b->d_wstart,
+        &b->d_flagbits,
         &b->d_ovf, &b->d_ovf_hi, &b->d_ovf_lo, &b->d_ovf_heads, &b->d_ovf_job, &b->d_ovf_fm, &b->d_jobs,
         &b->d_lens, &b->d_stamps, &b->d_big_desc, &b->d_big_out, &b->d_rhi, &b->d_rlo, &b->d_cnt_send, &b->d_cnt_recv,
         &b->d_seg_start, &b->d_seg_len, &b->d_vstart, &b->d_xs, &b->d_hv_keys, &b->d_hv_rec, &b->d_hv_len, &b->d_hv_s0,
