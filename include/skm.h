@@ -362,7 +362,8 @@ typedef struct skm_kept_db_opts {
                                recall lookup at load 0.6 measured 31-41 % slower than on the host
                                path's table, at 0.5 5-16 % slower, at 0.4 8-13 % faster
                                                                            */
-    int32_t  release_work;  /* 1: free the build handle's per-pass work buffers first (below)   */
+    int32_t  release_work;  /* 1: free the build handle's per-pass work buffers first (below);
+                               2: the same, but keep the resident sequences (skm_build_recall)  */
     uint64_t slots;         /* 0 = from load_pct; else exactly this many slots (> n); tests and
                                callers that size the table themselves                           */
 } skm_kept_db_opts;
@@ -381,7 +382,9 @@ typedef struct skm_kept_db_opts {
  * skm_build_finish, _finish_slice, _signature_flags and _counters return what they returned before,
  * and every call that would need the freed buffers -- skm_build_add_batch, _reserve, _prepare,
  * _run, _group_run, and a finish after skm_build_set_option -- returns SKM_E_STATE.  Such a handle
- * is only read out and destroyed. */
+ * is only read out and destroyed.  release_work = 2 frees the same buffers except the residues and
+ * the sequence table, which skm_build_recall reads; the same calls return SKM_E_STATE afterwards.  A
+ * later release_work = 1 frees those two as well.  Other non-zero values return SKM_E_ARG. */
 int skm_build_kept_db(skm_build* b, const skm_kept_db_opts* opts, skm_db** out);
 
 /* host only: the table skm_build_kept_db would allocate for n keys */
@@ -443,7 +446,7 @@ int skm_mph_build_device_ex(const uint64_t* keys, const skm_stored_kmer_data* da
  * file round trip of skm_build_finish + skm_mph_build_device + skm_db_open. */
 typedef struct skm_mph_db_opts {
     uint32_t seed;          /* as skm_mph_build_device's seed                                   */
-    int32_t  release_work;  /* as skm_kept_db_opts.release_work, the same contract              */
+    int32_t  release_work;  /* as skm_kept_db_opts.release_work, the same contract (0, 1, 2)    */
     int32_t  verify;        /* as skm_mph_build_device_ex's verify                              */
     int32_t  pad;
     const char* mph_path;   /* NULL = not written                                               */
@@ -763,6 +766,71 @@ int skm_annotate_fasta_best(skm_db* db, const uint8_t* bytes, const uint64_t* fi
 int skm_debug_best_calls(const skm_kmer_call* calls, const uint64_t* call_off, size_t n_seqs,
                          const skm_fidx* fx, int device, skm_best_call* best, uint8_t* deferred, float* ms);
 void skm_best_calls_free(skm_best_calls* c);
+
+/* ------------------------------------------------------------------------------------------
+ * Recall pass over a build's resident sequences.  Replaces the recall loop of
+ * kmers-build-signatures.cc:266-349 (every training protein through process_aa_seq +
+ * find_best_call against the DB just built) without the second host pack and upload of the
+ * proteins: the build already holds them in HBM in the layout a query uses (raw letters, one 0
+ * byte after each sequence, 64 zero bytes at the end), so a batch is a view into that buffer and
+ * the annotate pipeline runs on it in place.  A DB goes in; 16 bytes per sequence (or the calls)
+ * come out.  Nothing is copied device to device and no residue crosses PCIe.  With
+ * skm_build_kept_db, skm_build_mph_db and skm_build_write_final_kmers this is the fourth user of
+ * the build's resident data, and the only one that reads its input side.
+ *
+ * Resident sequences: those added with seq_func != 0xFFFF, in add order over all
+ * skm_build_add_batch calls (the others are dropped on the host by add_batch).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct skm_recall_opts {
+    uint64_t batch_residues; /* 0 = default (2^29: about 7 B of query scratch per residue, so under 4 GB
+                                a batch -- a plan, not a measured optimum).  A batch is a run of whole
+                                resident sequences whose packed bytes (len + 1 each) do not exceed it; a
+                                sequence that alone exceeds it is a batch of its own.  Values above 2^31
+                                are taken as 2^31 */
+    uint64_t first_seq, n_seqs; /* range of resident sequences; n_seqs 0 = to the end */
+} skm_recall_opts;
+typedef struct skm_recall_stats {
+    uint64_t n_seqs, n_windows, n_calls, n_deferred, n_batches, resident_bytes;
+    float view_ms, lookup_ms, calls_ms, best_ms;   /* device time summed over the batches */
+    double wall_s;
+} skm_recall_stats;
+/* kmers-build-signatures.cc:266-349 reads its proteins from the FASTA files again; here: how many
+ * sequences the handle holds and their packed bytes (len + 1 each).  Zeros once they were released
+ * (release_work = 1).  Host only. */
+int skm_build_resident_seqs(skm_build* b, uint64_t* n_seqs, uint64_t* n_residue_bytes);
+/* kmers-build-signatures.cc:266-349 over the resident sequences [first_seq, first_seq + n_seqs) of b
+ * against db, batch by batch through the query object db keeps for skm_annotate (its buffers only
+ * grow; per batch the host waits where skm_query_run waits, plus once for the batch's results).
+ * best and calls may each be NULL, not both: best[s] is what skm_annotate_best gives for sequence
+ * first_seq + s (sequences the best-call kernel declines are resolved as skm_query_best_calls
+ * resolves them; needs fx with device tables on b's device, else SKM_E_ARG), calls is what
+ * skm_annotate gives (CSR, call_off global over the range).  Release them with skm_best_calls_free /
+ * skm_calls_free.  db: any skm_db on b's device -- BDZ, host-built exact, or skm_build_kept_db's
+ * table; another device is SKM_E_ARG.  ropts NULL = defaults; a range outside the resident
+ * sequences is SKM_E_ARG.  stats may be NULL.
+ * SKM_E_STATE: b is not prepared (sequences added since the last prepare included); world_size > 1
+ * (a rank holds its shard's sequences only); the sequences were released (release_work = 1; the
+ * message names release_work -- release_work = 2 keeps them: every buffer 1 frees except the
+ * residues and the sequence table, and the same calls return SKM_E_STATE afterwards.  At the 50 M
+ * proteins of the headline build that keeps about 17.3 GB; by DESIGN.md section 4's figures it fits
+ * beside the 115.6 GB table, which nobody has run).  A build with no resident sequences gives zero
+ * results and launches nothing.
+ * The call first waits for everything the build's streams still have in flight.  It reads the
+ * residues, the sequence table and the host copy of the table, and writes only db's query object;
+ * but like every call on a handle it is made from the one host thread that drives b, so it does not
+ * run beside skm_build_write_final_kmers on b: a caller runs the two one after the other.
+ * write_final_kmers sizes its chunk from 3/4 of the memory free at its call and frees it before it
+ * returns, so the recall's batch buffers are allocated either before it (and are counted out of
+ * that free memory) or after it (and have the chunk's memory back); either order fits. */
+int skm_build_recall(skm_build* b, skm_db* db, const skm_annot_opts* aopts, const skm_recall_opts* ropts,
+                     const skm_fidx* fx, skm_best_calls* best, skm_calls* calls, skm_recall_stats* stats);
+/* host only (the cut rule of skm_build_recall, csrc/skm_recallplan.h; kmers-build-signatures.cc:
+ * 266-349 has no batches): the batches of the range over n_total sequences of these lengths, packed
+ * as the build packs them.  *n_batches = how many; for the first cap of them out[6 i ..] = first
+ * sequence, sequences, base (the view's start: the first sequence's packed start & ~15), that packed
+ * start, the packed end (after the last separator), windows. */
+int skm_recall_plan(const uint32_t* seq_len, uint64_t n_total, uint64_t batch_residues, uint64_t first_seq,
+                    uint64_t n_seqs, uint64_t* out, uint64_t cap, uint64_t* n_batches);
 
 #ifdef __cplusplus
 }

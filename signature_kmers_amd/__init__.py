@@ -111,6 +111,16 @@ class _FinalKmersStats(C.Structure):
                 ("d2h_ms", C.c_float), ("wide_index", C.c_uint32)]
 
 
+class _RecallOpts(C.Structure):
+    _fields_ = [("batch_residues", C.c_uint64), ("first_seq", C.c_uint64), ("n_seqs", C.c_uint64)]
+
+
+class _RecallStats(C.Structure):
+    _fields_ = [("n_seqs", C.c_uint64), ("n_windows", C.c_uint64), ("n_calls", C.c_uint64), ("n_deferred", C.c_uint64),
+                ("n_batches", C.c_uint64), ("resident_bytes", C.c_uint64), ("view_ms", C.c_float),
+                ("lookup_ms", C.c_float), ("calls_ms", C.c_float), ("best_ms", C.c_float), ("wall_s", C.c_double)]
+
+
 class _Pairs(C.Structure):
     _fields_ = [("pairs", C.POINTER(C.c_uint32)), ("n", C.c_uint64), ("n_hits", C.c_uint64)]
 
@@ -217,6 +227,11 @@ _SIGS = {
                                           C.POINTER(_FastaTable)]),
     "skm_debug_best_calls": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, _P, _P, C.POINTER(C.c_float)]),
     "skm_best_calls_free": (None, [C.POINTER(_BestCalls)]),
+    "skm_build_resident_seqs": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "skm_build_recall": (C.c_int, [_P, _P, C.POINTER(_AnnotOpts), C.POINTER(_RecallOpts), _P, C.POINTER(_BestCalls),
+                                   C.POINTER(_Calls), C.POINTER(_RecallStats)]),
+    "skm_recall_plan": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P, C.c_uint64,
+                                  C.POINTER(C.c_uint64)]),
 }
 
 _lib = None
@@ -502,18 +517,80 @@ class SignatureBuilder:
         _check(lib().skm_build_signature_flags(self._h, _ptr(out), n))
         return out[:n]
 
-    def kept_db(self, load_pct: int = 0, slots: int = 0, release_work: bool = False) -> "DeviceKeptKmerDb":
+    @staticmethod
+    def _release_level(release_work) -> int:
+        """release_work of kept_db / mph_db: False / True / 2 / "keep_sequences" -> 0 / 1 / 2."""
+        if isinstance(release_work, str):
+            if release_work != "keep_sequences":
+                raise SkmError(f"release_work: unknown value {release_work!r} (False, True, 2 or 'keep_sequences')")
+            return 2
+        if isinstance(release_work, (bool, np.bool_)):
+            return 1 if release_work else 0
+        if release_work in (0, 1, 2):
+            return int(release_work)
+        raise SkmError(f"release_work: unknown value {release_work!r} (False, True, 2 or 'keep_sequences')")
+
+    def resident_seqs(self) -> tuple:
+        """skm_build_resident_seqs: (sequences the handle holds -- those added with a kept function, in
+        add order -- , their packed bytes, len + 1 each); zeros once release_work=True freed them."""
+        n, nb = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().skm_build_resident_seqs(self._h, C.byref(n), C.byref(nb)))
+        return int(n.value), int(nb.value)
+
+    def recall(self, db: "CmphKmerDb", tables: "FunctionIndexTables | None" = None, *, want_calls: bool = False,
+               hypo_index=..., ignore_hypo: bool = False, min_hits: int = 5, max_gap: int = 200,
+               batch_residues: int = 0, first_seq: int = 0, n_seqs: int = 0):
+        """skm_build_recall: the recall pass (kmers-build-signatures.cc:266-349) over the resident
+        sequences [first_seq, first_seq + n_seqs) against db, read in place from the build's HBM
+        buffers -- no second upload of the proteins.  With tables: a BestCalls (what
+        FunctionCaller.best_seqs gives for the same sequences); with want_calls: (call_off, calls)
+        as QueryBatch.calls gives; with both: (BestCalls, call_off, calls).  The result carries
+        .stats (skm_recall_stats).  hypo_index defaults to "hypothetical protein" in the tables'
+        function index (-1 without tables or without that name)."""
+        if tables is None and not want_calls:
+            raise SkmError("recall: nothing asked for (tables=None and want_calls=False)")
+        if hypo_index is ...:
+            hypo_index = -1
+            if tables is not None and "hypothetical protein" in tables.function_index:
+                hypo_index = tables.function_index.index("hypothetical protein")
+        opts = _AnnotOpts(int(min_hits), int(max_gap), int(bool(ignore_hypo)), int(hypo_index), 0, 0)
+        ro = _RecallOpts(int(batch_residues), int(first_seq), int(n_seqs))
+        best = _BestCalls() if tables is not None else None
+        calls = _Calls() if want_calls else None
+        st = _RecallStats()
+        _check(lib().skm_build_recall(self._h, db._h, C.byref(opts), C.byref(ro), tables._h if tables is not None else None,
+                                      C.byref(best) if best is not None else None,
+                                      C.byref(calls) if calls is not None else None, C.byref(st)))
+        stats = {n: getattr(st, n) for n, _ in _RecallStats._fields_}
+        parts = []
+        if best is not None:
+            parts.append(_best_result(best, tables))
+        if calls is not None:
+            try:
+                n, nc = int(calls.n_seqs), int(calls.n_calls)
+                parts.append(np.ctypeslib.as_array(calls.call_off, shape=(n + 1,)).copy())
+                parts.append(np.frombuffer(C.string_at(calls.calls, CALL_DTYPE.itemsize * nc), dtype=CALL_DTYPE).copy()
+                             if nc else np.zeros(0, CALL_DTYPE))
+            finally:
+                lib().skm_calls_free(C.byref(calls))
+        res = parts[0] if len(parts) == 1 else _RecallResult(parts)
+        res.stats = stats
+        return res
+
+    def kept_db(self, load_pct: int = 0, slots: int = 0, release_work=False) -> "DeviceKeptKmerDb":
         """skm_build_kept_db: the exact-key DB (KeptKmerDB<8>) over the kept k-mers of the last run,
         built on the device from the resident arena -- no host copy of the kept set.  load_pct /
         slots size its range-reduced table (kept_db_plan); release_work frees the handle's per-pass
         work buffers first, after which the handle can only be read out (finish, finish_slice,
-        signature_flags, counters) and closed: run / prepare / add_batch raise SkmError."""
-        opts = _KeptDbOpts(int(load_pct), 1 if release_work else 0, int(slots))
+        signature_flags, counters) and closed: run / prepare / add_batch raise SkmError.
+        release_work=2 (or "keep_sequences") frees the same except the resident sequences, which
+        recall() reads."""
+        opts = _KeptDbOpts(int(load_pct), self._release_level(release_work), int(slots))
         h = C.c_void_p()
         _check(lib().skm_build_kept_db(self._h, C.byref(opts), C.byref(h)))
         return DeviceKeptKmerDb(h, self.device)
 
-    def mph_db(self, seed: int = 1, release_work: bool = False, verify: bool = False, mph_path: str | None = None,
+    def mph_db(self, seed: int = 1, release_work=False, verify: bool = False, mph_path: str | None = None,
                dat_path: str | None = None) -> "CmphKmerDb":
         """skm_build_mph_db: the BDZ signature DB (build_perfect_hash + CmphKmerDb, perfect_hash.h:11-69,
         cmph_kmer.h:95-104) over the kept k-mers of the last run, built and opened on the device from
@@ -521,7 +598,7 @@ class SignatureBuilder:
         .dat, written only where a path is given, are those of mph_build(sorted kept set, seed,
         device=...).  release_work as in kept_db.  The returned DB is independent of the builder; its
         `stats` are mph_build_device's dict (upload_s stays 0)."""
-        opts = _MphDbOpts(int(seed), 1 if release_work else 0, 1 if verify else 0, 0,
+        opts = _MphDbOpts(int(seed), self._release_level(release_work), 1 if verify else 0, 0,
                           mph_path.encode() if mph_path else None, dat_path.encode() if dat_path else None)
         h = C.c_void_p()
         st = _MphStats()
@@ -576,6 +653,24 @@ class SignatureBuilder:
             self.close()
         except Exception:
             pass
+
+
+class _RecallResult(tuple):
+    """SignatureBuilder.recall's tuple results, with the call's .stats."""
+
+
+def recall_plan(seq_len, batch_residues: int = 0, first_seq: int = 0, n_seqs: int = 0) -> list:
+    """skm_recall_plan (host only, no HIP call): the batches SignatureBuilder.recall cuts for resident
+    sequences of these lengths -- a list of dicts first, n, base, pstart, end, windows (base = the
+    batch's view start: its first sequence's packed start & ~15; end = after its last separator)."""
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    nb = C.c_uint64(0)
+    args = (_ptr(seq_len) if len(seq_len) else None, len(seq_len), int(batch_residues), int(first_seq), int(n_seqs))
+    _check(lib().skm_recall_plan(*args, None, 0, C.byref(nb)))
+    out = np.zeros((max(int(nb.value), 1), 6), np.uint64)
+    _check(lib().skm_recall_plan(*args, _ptr(out), int(nb.value), C.byref(nb)))
+    names = ("first", "n", "base", "pstart", "end", "windows")
+    return [dict(zip(names, (int(v) for v in row))) for row in out[:int(nb.value)]]
 
 
 class GlooTransport:

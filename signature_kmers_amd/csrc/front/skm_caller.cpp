@@ -244,11 +244,23 @@ int best_calls_batch(const skm_calls& calls, const std::vector<const FastaFile*>
     return first_rc;
 }
 
+namespace {
+int compose_best_where(const skm_best_calls& best, const std::vector<std::pair<size_t, size_t>>& where, const skm_fidx* fx,
+                       int n_threads, const std::vector<std::vector<SeqCall>*>& out, std::string& err);
+}
+
 int compose_best_batch(const skm_best_calls& best, const std::vector<const FastaFile*>& files, const skm_fidx* fx,
                        int n_threads, const std::vector<std::vector<SeqCall>*>& out, std::string& err) {
     std::vector<std::pair<size_t, size_t>> where;  // (file, record) per batch sequence
     for (size_t f = 0; f < files.size(); ++f)
         for (size_t r = 0; r < files[f]->size(); ++r) where.emplace_back(f, r);
+    return compose_best_where(best, where, fx, n_threads, out, err);
+}
+
+namespace {
+// best[s] is the call of record where[s].second of file where[s].first
+int compose_best_where(const skm_best_calls& best, const std::vector<std::pair<size_t, size_t>>& where, const skm_fidx* fx,
+                       int n_threads, const std::vector<std::vector<SeqCall>*>& out, std::string& err) {
     if (where.size() != best.n_seqs) {
         err = "best calls: the result does not match the batch";
         return SKM_E_STATE;
@@ -285,6 +297,107 @@ int compose_best_batch(const skm_best_calls& best, const std::vector<const Fasta
     for (auto& t : th) t.join();
     if (first_rc) err = "skm_best_call_name failed";
     return first_rc;
+}
+}  // namespace
+
+int call_files_resident(skm_build* b, skm_db* db, const std::vector<const FastaFile*>& files,
+                        const std::vector<BuildBatch>& batches, const std::vector<std::string>& function_index,
+                        int n_threads, const skm_fidx* fx, std::vector<std::vector<SeqCall>>& out, std::string& err,
+                        ResidentRecall* stats, uint64_t max_batch_residues) {
+    ResidentRecall st;
+    skm_annot_opts o{};
+    if (!annot_opts_for(function_index, false, o, err)) return SKM_E_ARG;
+    if (batches.size() != files.size()) {
+        err = "resident recall: one selection per file is needed";
+        return SKM_E_ARG;
+    }
+    out.assign(files.size(), std::vector<SeqCall>());
+    std::vector<std::vector<SeqCall>*> outp;
+    for (size_t f = 0; f < files.size(); ++f) {
+        out[f].resize(files[f]->size());
+        outp.push_back(&out[f]);
+    }
+    // the resident sequences in add order = the selections in file order; the rest of the records
+    std::vector<std::pair<size_t, size_t>> res_where, up_where;
+    for (size_t f = 0; f < files.size(); ++f) {
+        size_t k = 0;
+        const std::vector<uint32_t>& rec = batches[f].rec;
+        for (size_t r = 0; r < files[f]->size(); ++r) {
+            if (k < rec.size() && rec[k] == r) {
+                res_where.emplace_back(f, r);
+                ++k;
+            } else {
+                up_where.emplace_back(f, r);
+            }
+        }
+        if (k != rec.size()) {
+            err = "resident recall: the selection of " + files[f]->path + " does not ascend over its records";
+            return SKM_E_STATE;
+        }
+    }
+    uint64_t n_res = 0;
+    int rc = skm_build_resident_seqs(b, &n_res, nullptr);
+    if (!rc && n_res != res_where.size()) {
+        err = "resident recall: the build holds " + std::to_string(n_res) + " sequences, the selections name " +
+              std::to_string(res_where.size());
+        return SKM_E_STATE;
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    skm_best_calls best{};
+    skm_recall_stats rs{};
+    if (!rc) rc = skm_build_recall(b, db, &o, nullptr, fx, &best, nullptr, &rs);
+    st.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc) {
+        err = skm_last_error();
+        return rc;
+    }
+    st.resident_seqs = rs.n_seqs;
+    st.batches = rs.n_batches;
+    st.deferred = rs.n_deferred;
+    rc = compose_best_where(best, res_where, fx, n_threads, outp, err);
+    skm_best_calls_free(&best);
+    if (rc) return rc;
+    // the left-out records, packed as skm_annotate lays a batch out, up to max_batch_residues a batch
+    st.uploaded_seqs = up_where.size();
+    for (size_t s0 = 0; s0 < up_where.size();) {
+        size_t s1 = s0;
+        uint64_t bytes = 0;
+        while (s1 < up_where.size()) {
+            const uint64_t add = (uint64_t)files[up_where[s1].first]->len[up_where[s1].second] + 1;
+            if (s1 > s0 && bytes + add > max_batch_residues) break;
+            bytes += add;
+            ++s1;
+        }
+        PackedBatch pb;
+        pb.res.reset(new uint8_t[std::max<uint64_t>(bytes, 1)]);
+        pb.off.resize(s1 - s0);
+        pb.len.resize(s1 - s0);
+        uint64_t p = 0;
+        for (size_t s = s0; s < s1; ++s) {
+            const FastaFile& F = *files[up_where[s].first];
+            const size_t r = up_where[s].second;
+            std::memcpy(pb.res.get() + p, F.residues.data() + F.off[r], F.len[r]);
+            pb.res[p + F.len[r]] = 0;
+            pb.off[s - s0] = p;
+            pb.len[s - s0] = F.len[r];
+            p += (uint64_t)F.len[r] + 1;
+        }
+        t0 = std::chrono::steady_clock::now();
+        rc = skm_annotate_best(db, pb.res.get(), pb.off.data(), pb.len.data(), pb.off.size(), &o, fx, &best);
+        st.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (rc) {
+            err = skm_last_error();
+            return rc;
+        }
+        st.deferred += best.n_deferred;
+        const std::vector<std::pair<size_t, size_t>> where(up_where.begin() + s0, up_where.begin() + s1);
+        rc = compose_best_where(best, where, fx, n_threads, outp, err);
+        skm_best_calls_free(&best);
+        if (rc) return rc;
+        s0 = s1;
+    }
+    if (stats) *stats = st;
+    return SKM_OK;
 }
 
 int call_files(skm_db* db, const std::vector<const FastaFile*>& files, const std::vector<std::string>& function_index,

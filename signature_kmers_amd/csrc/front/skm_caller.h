@@ -80,4 +80,20 @@ int best_calls_batch(const skm_calls& calls, const std::vector<const FastaFile*>
                      const std::vector<const char*>& fidx, int n_threads, const std::vector<std::vector<SeqCall>*>& out,
                      std::string& err);
 
+
+// kmers-build-signatures --recall-source device: the recall pass with the records that were
+// selected into the build read in place from the build's resident sequences (skm_build_recall: no
+// second pack and upload of them), and only the records select_build_sequences left out -- no
+// function, an unkept function, a deleted fid -- uploaded as call_files uploads them.  batches[f] is
+// files[f]'s selection as it was added to b (every file, in order).  find_best_call runs on the
+// device for both sets (fx must hold device tables); out[f][r] as call_files fills it.
+struct ResidentRecall {
+    uint64_t resident_seqs = 0, uploaded_seqs = 0, batches = 0, deferred = 0;
+    double device_ms = 0;  // wall ms in skm_build_recall and skm_annotate_best
+};
+int call_files_resident(skm_build* b, skm_db* db, const std::vector<const FastaFile*>& files,
+                        const std::vector<BuildBatch>& batches, const std::vector<std::string>& function_index,
+                        int n_threads, const skm_fidx* fx, std::vector<std::vector<SeqCall>>& out, std::string& err,
+                        ResidentRecall* stats, uint64_t max_batch_residues = 2000000000ull);
+
 }  // namespace skmf

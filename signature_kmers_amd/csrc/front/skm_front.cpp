@@ -884,6 +884,7 @@ void select_build_sequences(const FunctionMap& fm, const FastaFile& f, unsigned 
         out.len.push_back(f.len[r]);
         out.func.push_back(fi);
         out.seq_id.push_back(seq_id);
+        out.rec.push_back((uint32_t)r);
     }
 }
 

@@ -132,6 +132,7 @@ struct BuildBatch {
     std::vector<uint32_t> len;
     std::vector<uint16_t> func;
     std::vector<uint32_t> seq_id;
+    std::vector<uint32_t> rec;  // the file's record index of each selected sequence
 };
 void select_build_sequences(const FunctionMap& fm, const FastaFile& f, unsigned file_number,
                             unsigned max_seqs_per_file, const std::set<std::string>& deleted_fids,

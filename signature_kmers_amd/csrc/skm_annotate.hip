@@ -36,6 +36,7 @@
 #include "skm_lookup.h"
 #include "skm_mphdb.h"
 #include "skm_pool.h"
+#include "skm_recall.h"
 #include "skm_select.h"
 #include "skm_util.h"
 
@@ -988,6 +989,19 @@ __global__ void k_zero_seps(const QMeta* __restrict__ meta, uint32_t n, uint8_t*
     if (s < n) res[meta[s].pstart + meta[s].len] = 0;
 }
 
+// skm_build_recall: a batch of a build's resident sequences as a query.  One thread per sequence:
+// its record of the build's table (u64 pstart, u32 len, then the function index, not read) becomes
+// the QMeta of the view that starts `base` bytes into the residues, and its window count the input
+// of the scan that gives the scratch offsets.
+__global__ void k_recall_view(const QMeta* __restrict__ seqs, uint32_t n, uint64_t base, QMeta* __restrict__ meta,
+                              uint32_t* __restrict__ nwin) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const QMeta m = seqs[s];
+    meta[s] = QMeta{m.pstart - base, m.len, 0u};
+    nwin[s] = m.len >= 8 ? m.len - 7 : 0;
+}
+
 // the b == 7 (g word, rank) pair lines from g and the rank table (defined with the BDZ builder)
 __global__ void k_mph_blk(const uint32_t* __restrict__ g, uint64_t gwords, const uint32_t* __restrict__ rank,
                           uint64_t nrank, uint64_t nblk, uint32_t* __restrict__ blk);
@@ -1003,6 +1017,10 @@ struct skm_query {
     float last_ms[5] = {};
     uint32_t nseq = 0;
     uint64_t rp = 0, n_windows = 0;
+    // skm_build_recall: the residues are read here instead of in d_res -- a view into a build's
+    // buffer, which the query neither owns, frees nor writes; the next upload or parse resets it
+    const uint8_t* res_view = nullptr;
+    hipEvent_t ev_view[2] = {};
     DevBuf d_res, d_meta, d_hits, d_scr, d_scr_off, d_caps, d_cap_off, d_slots, d_counts, d_call_off, d_calls;
     DevBuf d_seg_off, d_segs, d_segres, d_pool_ctr;
     Scanner scan;
@@ -1150,22 +1168,23 @@ void query_run(skm_query* q, const skm_annot_opts* o) {
     skm_db* db = q->db;
     SKM_HIP(hipSetDevice(db->device));
     hipStream_t st = q->stream;
+    const uint8_t* res = q->res_view ? q->res_view : q->d_res.as<uint8_t>();
     SKM_HIP(hipEventRecord(q->ev[0], st));
     if (q->rp && db->m) {
         uint64_t nthreads = ceil_div(q->rp, LK_POS);
         uint32_t grid = (uint32_t)std::min<uint64_t>(ceil_div(nthreads, LK_THREADS), 256ull * 16);
         if (db->exact && db->dev.xslots)
-            hipLaunchKernelGGL(k_lookup<LK_EXACTR>, dim3(grid), dim3(LK_THREADS), 0, st, q->d_res.as<uint8_t>(),
-                               q->rp, db->dev, q->d_hits.as<uint32_t>());
+            hipLaunchKernelGGL(k_lookup<LK_EXACTR>, dim3(grid), dim3(LK_THREADS), 0, st, res, q->rp, db->dev,
+                               q->d_hits.as<uint32_t>());
         else if (db->exact)
-            hipLaunchKernelGGL(k_lookup<LK_EXACT>, dim3(grid), dim3(LK_THREADS), 0, st, q->d_res.as<uint8_t>(),
-                               q->rp, db->dev, q->d_hits.as<uint32_t>());
+            hipLaunchKernelGGL(k_lookup<LK_EXACT>, dim3(grid), dim3(LK_THREADS), 0, st, res, q->rp, db->dev,
+                               q->d_hits.as<uint32_t>());
         else if (db->dev.b == 7)
-            hipLaunchKernelGGL(k_lookup<LK_BDZ7>, dim3(grid), dim3(LK_THREADS), 0, st, q->d_res.as<uint8_t>(),
-                               q->rp, db->dev, q->d_hits.as<uint32_t>());
+            hipLaunchKernelGGL(k_lookup<LK_BDZ7>, dim3(grid), dim3(LK_THREADS), 0, st, res, q->rp, db->dev,
+                               q->d_hits.as<uint32_t>());
         else
-            hipLaunchKernelGGL(k_lookup<LK_BDZ>, dim3(grid), dim3(LK_THREADS), 0, st, q->d_res.as<uint8_t>(),
-                               q->rp, db->dev, q->d_hits.as<uint32_t>());
+            hipLaunchKernelGGL(k_lookup<LK_BDZ>, dim3(grid), dim3(LK_THREADS), 0, st, res, q->rp, db->dev,
+                               q->d_hits.as<uint32_t>());
     } else if (q->rp) {
         SKM_HIP(hipMemsetAsync(q->d_hits.p, 0xFF, 4 * q->rp, st));
     }
@@ -1528,6 +1547,7 @@ void query_setup(skm_query* q, const uint8_t* residues, const uint64_t* seq_off,
     SKM_HIP(hipSetDevice(q->db->device));
     query_stream(q);
     q->ran = false;
+    q->res_view = nullptr;
     q->n_calls = 0;
     std::vector<QMeta> meta(n_seqs);
     std::vector<uint64_t> scr_off(n_seqs);
@@ -1599,6 +1619,7 @@ void query_setup_fasta(skm_query* q, const uint8_t* bytes, const uint64_t* file_
     SKM_HIP(hipSetDevice(q->db->device));
     query_stream(q);
     q->ran = false;
+    q->res_view = nullptr;
     q->n_calls = 0;
     q->nseq = 0;
     q->rp = q->n_windows = 0;
@@ -1706,6 +1727,8 @@ void skm_query_destroy(skm_query* q) {
     (void)hipSetDevice(q->db->device);
     if (q->stream) (void)hipStreamSynchronize(q->stream);
     for (auto& e : q->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : q->ev_view)
         if (e) (void)hipEventDestroy(e);
     if (q->stream) (void)hipStreamDestroy(q->stream);
     delete q;
@@ -1831,6 +1854,127 @@ void skm_calls_free(skm_calls* c) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// The recall pass over a build's resident sequences (skm_build_recall; the recall loop of
+// kmers-build-signatures.cc:266-349 without its second copy of the training proteins).  The build's
+// residue buffer already has a query's layout, so a batch is a view of it: base = the first
+// sequence's start rounded down to 16 (k_lookup loads aligned 16-byte units and indexes hits by
+// position), k_recall_view writes the view's QMeta and window counts, the Scanner the scratch
+// offsets, and query_run runs as on an uploaded batch.  The bytes from base to the first sequence
+// are the previous sequence's tail: their hits are computed and never read.  Per batch the host
+// waits where query_run waits, plus once for the 16-byte bests or the calls.
+// ------------------------------------------------------------------------------------------
+namespace skm {
+
+int db_device(const skm_db* db) { return db->device; }
+
+void recall_resident(skm_db* db, const uint8_t* d_res, const void* d_meta, const std::vector<RecallBatch>& plan,
+                     const skm_annot_opts* o, const skm_fidx* fx, skm_best_calls* best, skm_calls* calls,
+                     skm_recall_stats* stats) {
+    SKM_HIP(hipSetDevice(db->device));
+    uint64_t n_seqs = 0;
+    for (const RecallBatch& bt : plan) n_seqs += bt.n;
+    if (best) {
+        std::memset(best, 0, sizeof(*best));
+        best->best = (skm_best_call*)std::malloc(sizeof(skm_best_call) * std::max<uint64_t>(n_seqs, 1));
+        SKM_CHECK(best->best, SKM_E_OOM, "host allocation failed");
+        best->n_seqs = n_seqs;
+    }
+    std::vector<skm_kmer_call> all_calls;
+    if (calls) {
+        std::memset(calls, 0, sizeof(*calls));
+        calls->call_off = (uint64_t*)std::malloc(8 * (n_seqs + 1));
+        SKM_CHECK(calls->call_off, SKM_E_OOM, "host allocation failed");
+        calls->call_off[0] = 0;
+        calls->n_seqs = n_seqs;
+    }
+    stats->n_seqs = n_seqs;
+    stats->n_batches = plan.size();
+    if (plan.empty()) {
+        if (calls) {
+            calls->calls = (skm_kmer_call*)std::malloc(sizeof(skm_kmer_call));
+            SKM_CHECK(calls->calls, SKM_E_OOM, "host allocation failed");
+        }
+        return;
+    }
+    if (!db->aq) {
+        db->aq = new skm_query();
+        db->aq->db = db;
+    }
+    skm_query* q = db->aq;
+    query_stream(q);
+    if (!q->ev_view[0])
+        for (auto& e : q->ev_view) SKM_HIP(hipEventCreate(&e));
+    hipStream_t st = q->stream;
+    uint64_t done = 0, n_calls = 0;
+    for (const RecallBatch& bt : plan) {
+        SKM_CHECK(bt.n < 0xFFFFFFFFull, SKM_E_ARG, "too many sequences in one recall batch");
+        const uint32_t ns = (uint32_t)bt.n;
+        q->ran = false;
+        q->n_calls = 0;
+        q->res_view = d_res + bt.base;
+        q->nseq = ns;
+        q->rp = bt.end - bt.base;
+        q->n_windows = bt.windows;
+        q->d_meta.ensure(sizeof(QMeta) * ns);
+        q->d_scr_off.ensure(8 * ((uint64_t)ns + 1));
+        query_run_buffers(q, ceil_div(q->rp + 1, LK_POS) * LK_POS);
+        // the window counts go through d_counts, which query_run writes only after it has read
+        // the scratch offsets made from them
+        SKM_HIP(hipEventRecord(q->ev_view[0], st));
+        hipLaunchKernelGGL(k_recall_view, dim3(ceil_div(ns, 256)), dim3(256), 0, st,
+                           reinterpret_cast<const QMeta*>(d_meta) + bt.first, ns, bt.base,
+                           q->d_meta.as<QMeta>(), q->d_counts.as<uint32_t>());
+        SKM_HIP(hipGetLastError());
+        q->scan.run(q->d_counts.as<uint32_t>(), ns, q->d_scr_off.as<uint64_t>(), st);
+        SKM_HIP(hipEventRecord(q->ev_view[1], st));
+        query_run(q, o);
+        float vms = 0.0f;
+        SKM_HIP(hipEventElapsedTime(&vms, q->ev_view[0], q->ev_view[1]));
+        stats->view_ms += vms;
+        stats->lookup_ms += q->last_ms[0];
+        stats->calls_ms += q->last_ms[1] + q->last_ms[2];
+        stats->n_windows += bt.windows;
+        if (best) {
+            float ms = 0.0f;
+            uint64_t nd = 0;
+            best_calls_into(q->d_calls.as<skm_kmer_call>(), q->d_call_off.as<uint64_t>(), ns, q->n_calls, fx, db->device,
+                            st, q->best, best->best + done, &ms, &nd);
+            stats->best_ms += ms;
+            stats->n_deferred += nd;
+        }
+        if (calls) {
+            all_calls.resize(n_calls + q->n_calls);
+            SKM_HIP(hipMemcpyAsync(calls->call_off + done, q->d_call_off.p, 8 * ((uint64_t)ns + 1), hipMemcpyDeviceToHost, st));
+            if (q->n_calls)
+                SKM_HIP(hipMemcpyAsync(all_calls.data() + n_calls, q->d_calls.p, sizeof(skm_kmer_call) * q->n_calls,
+                                       hipMemcpyDeviceToHost, st));
+            SKM_HIP(hipStreamSynchronize(st));
+            for (uint64_t s = 0; s <= ns; ++s) calls->call_off[done + s] += n_calls;
+        }
+        n_calls += q->n_calls;
+        done += ns;
+    }
+    q->res_view = nullptr;  // the view ends with the call: the build may free its residues
+    q->ran = false;
+    stats->n_calls = n_calls;
+    if (best) {
+        best->n_calls = n_calls;
+        best->n_windows = stats->n_windows;
+        best->n_deferred = stats->n_deferred;
+        best->kernel_ms = stats->best_ms;
+    }
+    if (calls) {
+        calls->calls = (skm_kmer_call*)std::malloc(sizeof(skm_kmer_call) * std::max<uint64_t>(n_calls, 1));
+        SKM_CHECK(calls->calls, SKM_E_OOM, "host allocation failed");
+        if (n_calls) std::memcpy(calls->calls, all_calls.data(), sizeof(skm_kmer_call) * n_calls);
+        calls->n_calls = n_calls;
+        calls->n_windows = stats->n_windows;
+    }
+}
+
+}  // namespace skm
 
 // ------------------------------------------------------------------------------------------
 // BDZ construction on the device (build_perfect_hash, perfect_hash.h:11-69, via cmph_new

@@ -118,31 +118,44 @@ BestWork::~BestWork() {
         if (e) (void)hipEventDestroy(e);
 }
 
-void best_calls_resident(const skm_kmer_call* d_calls, const uint64_t* d_call_off, uint64_t n_seqs, uint64_t n_calls,
-                         const skm_fidx* fx, int device, hipStream_t st, BestWork& w, skm_best_calls* out) {
+void best_calls_check(const skm_fidx* fx, int device) {
     SKM_CHECK(fx->device >= 0, SKM_E_ARG, "the function-index tables were made without a device (skm_fidx_create device < 0)");
     SKM_CHECK(fx->device == device, SKM_E_ARG, "the function-index tables were made for another device than the query's");
+}
+
+void best_calls_into(const skm_kmer_call* d_calls, const uint64_t* d_call_off, uint64_t n_seqs, uint64_t n_calls,
+                     const skm_fidx* fx, int device, hipStream_t st, BestWork& w, skm_best_call* h_best, float* ms,
+                     uint64_t* n_deferred) {
+    best_calls_check(fx, device);
+    SKM_CHECK(n_seqs < 0xFFFFFFFFull, SKM_E_ARG, "too many sequences in one batch");
+    launch_best(d_calls, d_call_off, n_seqs, n_calls, fx, st, w, h_best, ms);
+    uint64_t nd = 0;
+    for (uint64_t s = 0; s < n_seqs; ++s) nd += (h_best[s].flags & SKM_BEST_DEFERRED) != 0;
+    if (nd) {  // only now are calls downloaded: the deferred sequences' own
+        std::vector<uint64_t> off(n_seqs + 1);
+        SKM_HIP(hipMemcpyAsync(off.data(), d_call_off, 8 * (n_seqs + 1), hipMemcpyDeviceToHost, st));
+        SKM_HIP(hipStreamSynchronize(st));
+        std::vector<skm_kmer_call> c;
+        for (uint64_t s = 0; s < n_seqs; ++s) {
+            if (!(h_best[s].flags & SKM_BEST_DEFERRED)) continue;
+            c.resize(off[s + 1] - off[s]);
+            SKM_HIP(hipMemcpyAsync(c.data(), d_calls + off[s], sizeof(skm_kmer_call) * c.size(), hipMemcpyDeviceToHost, st));
+            SKM_HIP(hipStreamSynchronize(st));
+            resolve_deferred(fx, c.data(), c.size(), &h_best[s]);
+        }
+    }
+    *n_deferred = nd;
+}
+
+void best_calls_resident(const skm_kmer_call* d_calls, const uint64_t* d_call_off, uint64_t n_seqs, uint64_t n_calls,
+                         const skm_fidx* fx, int device, hipStream_t st, BestWork& w, skm_best_calls* out) {
+    best_calls_check(fx, device);
     SKM_CHECK(n_seqs < 0xFFFFFFFFull, SKM_E_ARG, "too many sequences in one batch");
     best_alloc(out, n_seqs);
     try {
         out->n_calls = n_calls;
-        launch_best(d_calls, d_call_off, n_seqs, n_calls, fx, st, w, out->best, &out->kernel_ms);
-        uint64_t nd = 0;
-        for (uint64_t s = 0; s < n_seqs; ++s) nd += (out->best[s].flags & SKM_BEST_DEFERRED) != 0;
-        if (nd) {  // only now are calls downloaded: the deferred sequences' own
-            std::vector<uint64_t> off(n_seqs + 1);
-            SKM_HIP(hipMemcpyAsync(off.data(), d_call_off, 8 * (n_seqs + 1), hipMemcpyDeviceToHost, st));
-            SKM_HIP(hipStreamSynchronize(st));
-            std::vector<skm_kmer_call> c;
-            for (uint64_t s = 0; s < n_seqs; ++s) {
-                if (!(out->best[s].flags & SKM_BEST_DEFERRED)) continue;
-                c.resize(off[s + 1] - off[s]);
-                SKM_HIP(hipMemcpyAsync(c.data(), d_calls + off[s], sizeof(skm_kmer_call) * c.size(), hipMemcpyDeviceToHost, st));
-                SKM_HIP(hipStreamSynchronize(st));
-                resolve_deferred(fx, c.data(), c.size(), &out->best[s]);
-            }
-        }
-        out->n_deferred = nd;
+        best_calls_into(d_calls, d_call_off, n_seqs, n_calls, fx, device, st, w, out->best, &out->kernel_ms,
+                        &out->n_deferred);
     } catch (...) {
         skm_best_calls_free(out);
         throw;

@@ -45,6 +45,7 @@
 #include "skm_mphdb.h"
 #include "skm_pool.h"
 #include "skm_output.h"
+#include "skm_recall.h"
 #include "skm_util.h"
 
 #if defined(SKM_WITH_RCCL)
@@ -5404,6 +5405,7 @@ struct skm_build {
     bool seqid_strict = true;
     bool prepared = false, ran = false;
     bool work_released = false;         // skm_build_kept_db(release_work): only the results are left
+    bool seqs_released = false;         //   release_work 1: d_res and d_meta went too (2 keeps them for skm_build_recall)
 
     // device input
     DevBuf d_res, d_meta, d_blk2seq, d_glen;
@@ -8419,11 +8421,21 @@ int skm_build_signature_flags(skm_build* b, uint8_t* out, uint64_t cap) {
 
 // skm_build_kept_db(release_work): every device buffer but what finish, finish_slice,
 // signature_flags and counters read -- the kept arena (d_keys, d_data), the statistics (d_ctr,
-// d_dfunc, d_swf) and the signature flags (d_flags) -- once nothing of the run is in flight
-static void release_work(skm_build* b) {
+// d_dfunc, d_swf) and the signature flags (d_flags) -- once nothing of the run is in flight.
+// level 2 keeps the resident sequences as well (d_res, d_meta: skm_build_recall reads them); a later
+// level 1 frees those too.
+static void release_work(skm_build* b, int level) {
+    SKM_CHECK(level == 1 || level == 2, SKM_E_ARG, "release_work must be 0, 1 or 2");
     SKM_HIP(hipDeviceSynchronize());
+    if (level == 1 && !b->seqs_released) {
+        b->d_res.release();
+        b->d_meta.release();
+        b->res_cap = 0;
+        b->seqs_released = true;
+    }
+    if (b->work_released) return;
     DevBuf* work[] = {
-        &b->d_res, &b->d_meta, &b->d_blk2seq, &b->d_glen, &b->d_hist, &b->d_offs, &b->d_partial, &b->d_rbbase,
+        &b->d_blk2seq, &b->d_glen, &b->d_hist, &b->d_offs, &b->d_partial, &b->d_rbbase,
         &b->d_bstart32, &b->d_bstart, &b->d_owner_start, &b->d_recs_hi, &b->d_recs_lo, &b->d_tmp_hi, &b->d_tmp_lo,
         &b->d_stg_hi, &b->d_stg_lo, &b->d_part_order, &b->d_cur0, &b->d_cur1, &b->d_slices, &b->d_cnt0, &b->d_wstart,
         &b->d_flagbits,
@@ -8451,7 +8463,7 @@ int skm_build_kept_db(skm_build* b, const skm_kept_db_opts* opts, skm_db** out) 
     SKM_HIP(hipSetDevice(b->device));
     if (!b->prepared || !b->ran) run_ranks(Ranks{b});
     const uint64_t slots = kept_db_slots(b->n_kept, opts);
-    if (opts && opts->release_work && !b->work_released) release_work(b);
+    if (opts && opts->release_work) release_work(b, opts->release_work);
     *out = db_from_device_kept(b->d_keys.as<uint64_t>(), b->d_data.as<skm_stored_kmer_data>(), b->n_kept, slots,
                                b->device, b->stream);
     SKM_API_END
@@ -8470,7 +8482,7 @@ int skm_build_mph_db(skm_build* b, const skm_mph_db_opts* opts, skm_db** out, sk
     if (!b->prepared || !b->ran) run_ranks(Ranks{b});
     uint64_t plan[4];
     mph_db_plan(b->n_kept, plan);  // more kept k-mers than one BDZ holds: SKM_E_ARG
-    if (o.release_work && !b->work_released) release_work(b);
+    if (o.release_work) release_work(b, o.release_work);
     if (b->n_kept < 1024) {  // skm_mph_build_device's small-size rule: the host builder over the sorted kept set
         skm_kept kept{};
         const int rc = skm_build_finish(b, &kept);
@@ -8488,6 +8500,70 @@ int skm_build_mph_db(skm_build* b, const skm_mph_db_opts* opts, skm_db** out, sk
     *out = db_from_device_mph(b->d_keys.as<uint64_t>(), b->d_data.as<skm_stored_kmer_data>(), b->n_kept, &o, b->device,
                               stats);
     SKM_API_END
+}
+
+int skm_build_resident_seqs(skm_build* b, uint64_t* n_seqs, uint64_t* n_residue_bytes) {
+    SKM_API_BEGIN
+    SKM_CHECK(b, SKM_E_ARG, "null build");
+    if (n_seqs) *n_seqs = b->seqs_released ? 0 : b->h_meta.size();
+    if (n_residue_bytes) *n_residue_bytes = b->seqs_released ? 0 : b->rp_total;
+    SKM_API_END
+}
+
+// the recall pass read in place from d_res / d_meta (skm_annotate.hip: recall_resident); this side
+// holds the state rules and cuts the batches from the host's copy of the table (skm_recallplan.h)
+int skm_build_recall(skm_build* b, skm_db* db, const skm_annot_opts* aopts, const skm_recall_opts* ropts,
+                     const skm_fidx* fx, skm_best_calls* best, skm_calls* calls, skm_recall_stats* stats) {
+    if (best) std::memset(best, 0, sizeof(*best));
+    if (calls) std::memset(calls, 0, sizeof(*calls));
+    skm_recall_stats st{};
+    int rc = SKM_OK;
+    try {
+        const auto t0 = std::chrono::steady_clock::now();
+        SKM_CHECK(b && db && aopts, SKM_E_ARG, "null argument");
+        SKM_CHECK(best || calls, SKM_E_ARG, "skm_build_recall: best and calls are both NULL");
+        SKM_CHECK(!best || fx, SKM_E_ARG, "skm_build_recall: best calls need the function-index tables");
+        SKM_CHECK(aopts->mean_mode == 0 || aopts->mean_mode == 1, SKM_E_ARG, "mean_mode must be 0 or 1");
+        SKM_CHECK(aopts->mad_mode == 0 || aopts->mad_mode == 1, SKM_E_ARG, "mad_mode must be 0 or 1");
+        SKM_CHECK(aopts->min_hits >= 1 && aopts->max_gap >= 0, SKM_E_ARG, "invalid min_hits / max_gap");
+        SKM_CHECK(b->world == 1, SKM_E_STATE,
+                  "skm_build_recall needs world_size 1: a rank holds only its own shard's sequences");
+        SKM_CHECK(!b->seqs_released, SKM_E_STATE,
+                  "the build's resident sequences were released (release_work = 1 of skm_build_kept_db / "
+                  "skm_build_mph_db; release_work = 2 keeps them for skm_build_recall)");
+        SKM_CHECK(b->prepared, SKM_E_STATE, "skm_build_recall needs a prepared build (skm_build_prepare)");
+        SKM_CHECK(db_device(db) == b->device, SKM_E_ARG, "skm_build_recall: the DB is on another device than the build");
+        if (best) best_calls_check(fx, b->device);
+        std::vector<RecallBatch> plan;
+        const SeqMeta* hm = b->h_meta.data();
+        SKM_CHECK(recall_plan([hm](uint64_t s) { return hm[s].len; }, b->h_meta.size(), ropts ? ropts->batch_residues : 0,
+                              ropts ? ropts->first_seq : 0, ropts ? ropts->n_seqs : 0, plan),
+                  SKM_E_ARG, "skm_build_recall: first_seq / n_seqs lie outside the resident sequences");
+        for (const RecallBatch& bt : plan)  // the shared rule against the table the device holds
+            SKM_CHECK(bt.pstart == hm[bt.first].pstart && bt.end <= b->rp, SKM_E_STATE,
+                      "skm_build_recall: the batch plan does not match the resident table");
+        st.resident_bytes = b->rp;
+        SKM_HIP(hipSetDevice(b->device));
+        // whatever the build's streams still have in flight (a run's tail, a hand-off) ends first
+        if (!plan.empty()) SKM_HIP(hipDeviceSynchronize());
+        recall_resident(db, b->d_res.as<uint8_t>(), b->d_meta.p, plan, aopts, fx, best, calls, &st);
+        st.wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } catch (const ::skm::Error& e) {
+        ::skm::set_last_error(e.what());
+        rc = e.code;
+    } catch (const std::bad_alloc&) {
+        ::skm::set_last_error("host allocation failed");
+        rc = SKM_E_OOM;
+    } catch (const std::exception& e) {
+        ::skm::set_last_error(e.what());
+        rc = SKM_E_ARG;
+    }
+    if (rc) {
+        if (best) skm_best_calls_free(best);
+        if (calls) skm_calls_free(calls);
+    }
+    if (stats) *stats = st;
+    return rc;
 }
 
 void skm_kept_free(skm_kept* k) {

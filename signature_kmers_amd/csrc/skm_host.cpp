@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "skm_recallplan.h"
 #include "skm_strutil.h"
 #include "skm_util.h"
 
@@ -91,6 +92,23 @@ int skm_device_mem_info(int device, uint64_t* free_bytes, uint64_t* total_bytes)
     SKM_HIP(hipMemGetInfo(&fr, &tot));
     *free_bytes = fr;
     *total_bytes = tot;
+    SKM_API_END
+}
+
+// host only: skm_build_recall's batch cuts for sequences of these lengths (skm_recallplan.h)
+int skm_recall_plan(const uint32_t* seq_len, uint64_t n_total, uint64_t batch_residues, uint64_t first_seq,
+                    uint64_t n_seqs, uint64_t* out, uint64_t cap, uint64_t* n_batches) {
+    SKM_API_BEGIN
+    SKM_CHECK((seq_len || !n_total) && n_batches && (out || !cap), SKM_E_ARG, "null argument");
+    std::vector<RecallBatch> plan;
+    SKM_CHECK(recall_plan([seq_len](uint64_t s) { return seq_len[s]; }, n_total, batch_residues, first_seq, n_seqs, plan),
+              SKM_E_ARG, "skm_recall_plan: first_seq / n_seqs lie outside the sequences");
+    *n_batches = plan.size();
+    for (uint64_t i = 0; i < plan.size() && i < cap; ++i) {
+        const RecallBatch& b = plan[i];
+        const uint64_t row[6] = {b.first, b.n, b.base, b.pstart, b.end, b.windows};
+        std::memcpy(out + 6 * i, row, sizeof(row));
+    }
     SKM_API_END
 }
 

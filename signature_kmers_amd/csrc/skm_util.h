@@ -110,6 +110,12 @@ struct BestWork {
 };
 void best_calls_resident(const skm_kmer_call* d_calls, const uint64_t* d_call_off, uint64_t n_seqs, uint64_t n_calls,
                          const skm_fidx* fx, int device, hipStream_t st, BestWork& w, skm_best_calls* out);
+// the same into a caller's array h_best[n_seqs] (a batch of a larger result: skm_build_recall), and
+// the argument check both make first (SKM_E_ARG: fx without device tables, or for another device)
+void best_calls_into(const skm_kmer_call* d_calls, const uint64_t* d_call_off, uint64_t n_seqs, uint64_t n_calls,
+                     const skm_fidx* fx, int device, hipStream_t st, BestWork& w, skm_best_call* h_best, float* ms,
+                     uint64_t* n_deferred);
+void best_calls_check(const skm_fidx* fx, int device);
 
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 inline int ilog2_ceil(uint64_t x) {

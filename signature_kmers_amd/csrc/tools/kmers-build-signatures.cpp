@@ -19,6 +19,11 @@
 // ones: skm_build_write_final_kmers; the file is the same).  With all three on `device` (or no
 // --perfect-hash) the kept set never comes to the host: skm_build_finish is not called, the three
 // stdout lines and distinct_functions come from skm_build_stats.
+// --recall-source host|device: the recall pass packs and uploads every training protein again, or
+// (device) reads the proteins that were selected into the build in place from the build's resident
+// sequences (skm_build_recall) and uploads only the records the selection left out; every output is
+// the same.  The build handle then lives until the recall is done, and keeps its sequences where
+// it releases its work buffers.
 // Multi-GPU: --n-gpus N forks one process per GPU (rank r on device r) before
 // any GPU or thread use; or, under an external launcher (RANK / WORLD_SIZE / LOCAL_RANK in the
 // environment, e.g. torchrun --no-python), each launched process is one rank and rank 0 hands the
@@ -184,7 +189,7 @@ int main(int argc, char** argv) {
                 {"n-gpus", 0, false, false},           {"comm", 0, false, false},
                 {"comm-file", 0, false, false},        {"recall-db", 0, false, false},
                 {"perfect-hash-source", 0, false, false}, {"best-call", 0, false, false},
-                {"final-kmers-source", 0, false, false}};
+                {"final-kmers-source", 0, false, false}, {"recall-source", 0, false, false}};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
     if (op.has("help")) {
@@ -217,6 +222,10 @@ int main(int argc, char** argv) {
                   << "                                       --recall-db device and --perfect-hash-source device (or no\n"
                   << "                                       --perfect-hash) the kept k-mers are never copied to the host\n"
                   << "  --best-call arg                      host (default) | device: where the recall pass runs find_best_call\n"
+                  << "  --recall-source arg                  host (default): the recall pass packs and uploads every protein again;\n"
+                  << "                                       device: the proteins selected into the build are recalled in place from\n"
+                  << "                                       the build's resident sequences, only the others are uploaded, and\n"
+                  << "                                       find_best_call runs on the device (one GPU; the outputs are the same)\n"
                   << "  -h [ --help ]                        show this help message\n";
         return 1;
     }
@@ -246,6 +255,12 @@ int main(int argc, char** argv) {
         die("--final-kmers-source device needs --final-kmers: it names the file the k-mers are written to");
     if (fk_source == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
         die("--final-kmers-source device needs one GPU: the kept k-mers of a multi-rank build are sharded over the ranks");
+    const std::string recall_source = op.get("recall-source", "host");
+    if (recall_source != "host" && recall_source != "device") die("--recall-source must be host or device");
+    if (recall_source == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
+        die("--recall-source device needs one GPU: a rank of a multi-rank build holds only its own shard's sequences");
+    const bool recall_resident = recall_source == "device";
+    const int release_level = recall_resident ? 2 : 1;  // 2 keeps the resident sequences for the recall
     // every consumer of the kept set on the device: no host copy of it is made
     const bool kept_on_device = fk_source == "device" && recall_db == "device" &&
                                 (ph_source == "device" || op.get("perfect-hash").empty());
@@ -491,7 +506,7 @@ int main(int argc, char** argv) {
         std::cerr << "build perfect hash into " << quoted(ph_file) << " with data in " << quoted(ph_data) << "\n";
         skm_mph_db_opts mo{};
         mo.seed = mph_seed;
-        mo.release_work = 1;
+        mo.release_work = release_level;
         mo.mph_path = ph_file.c_str();
         mo.dat_path = ph_data.c_str();
         skm_db* mdb = nullptr;
@@ -505,11 +520,12 @@ int main(int argc, char** argv) {
     skm_db* kdb = nullptr;
     if (recall_db == "device") {
         skm_kept_db_opts ko{};
-        ko.release_work = 1;
+        ko.release_work = release_level;
         check(skm_build_kept_db(b, &ko, &kdb), "skm_build_kept_db");
     }
-    // --final-kmers-source device: the handle lives until the final.kmers thread has written the file
-    if (fk_source != "device") {
+    // --final-kmers-source device: the handle lives until the final.kmers thread has written the file;
+    // --recall-source device: until the recall has read its sequences
+    if (fk_source != "device" && !recall_resident) {
         skm_build_destroy(b);
         b = nullptr;
     }
@@ -523,11 +539,12 @@ int main(int argc, char** argv) {
 
     std::thread final_kmers_thread;
     double t_final_kmers = 0;
-    if (!final_kmers.empty()) {
-        if (path_is_relative(final_kmers)) {
-            final_kmers = path_join(kmer_data_dir, final_kmers);
-            std::cerr << "Updated final_kmers to " << quoted(final_kmers) << "\n";
-        }
+    if (!final_kmers.empty() && path_is_relative(final_kmers)) {
+        final_kmers = path_join(kmer_data_dir, final_kmers);
+        std::cerr << "Updated final_kmers to " << quoted(final_kmers) << "\n";
+    }
+    auto start_final_kmers = [&]() {
+        if (final_kmers.empty()) return;
         final_kmers_thread = std::thread([&]() {
             const double tk = now_s();
             std::cerr << "writing kmers to " << quoted(final_kmers) << "\n";
@@ -538,7 +555,14 @@ int main(int argc, char** argv) {
             t_final_kmers = now_s() - tk;
             std::cerr << "writing kmers to " << quoted(final_kmers) << " complete\n";
         });
-    }
+    };
+    // A handle is driven by one thread at a time.  With --recall-source device and
+    // --final-kmers-source device both the recall and the dump use the build handle: the recall
+    // (tens of milliseconds of device time) goes first and the dump's thread starts after it, beside
+    // the reports; the recall's batch buffers are then allocated before the dump sizes its chunk
+    // from the memory that is free.
+    const bool dump_after_recall = recall_resident && fk_source == "device";
+    if (!dump_after_recall) start_final_kmers();
 
     {
         std::ofstream df(path_join(kmer_data_dir, "distinct_functions"));
@@ -579,10 +603,17 @@ int main(int argc, char** argv) {
     double recall_dev_ms = 0;
     uint64_t recall_deferred = 0;
     skm_fidx* fx = nullptr;  // --best-call device: find_best_call on the recall's resident calls
-    if (!best_call_tables(best_call, fidx, device, &fx, err)) die(err);
-    if (call_files(kdb, fptr, fidx, false, n_threads, calls, err, &recall_dev_ms, 2000000000ull, nullptr, nullptr, fx,
-                   &recall_deferred))
+    if (!best_call_tables(recall_resident ? "device" : best_call, fidx, device, &fx, err)) die(err);
+    ResidentRecall rr;
+    if (recall_resident) {
+        if (call_files_resident(b, kdb, fptr, batches, fidx, n_threads, fx, calls, err, &rr)) die(err);
+        if (dump_after_recall) start_final_kmers();
+        recall_dev_ms = rr.device_ms;
+        recall_deferred = rr.deferred;
+    } else if (call_files(kdb, fptr, fidx, false, n_threads, calls, err, &recall_dev_ms, 2000000000ull, nullptr, nullptr,
+                          fx, &recall_deferred)) {
         die(err);
+    }
     skm_fidx_destroy(fx);
     skm_db_close(kdb);
     {  // one report per file (kmers-build-signatures.cc:300-349), the files on the host threads
@@ -634,7 +665,11 @@ int main(int argc, char** argv) {
               << t_recall << " recall_device " << t_recall_dev << " total " << now_s() - t_start << " startup "
               << t_startup << " defs " << t_defs << " hip_init " << t_hip_init << " create " << t_create
               << " parse_files " << t_files << " fm_load " << t_fm << " recall_deferred " << recall_deferred
-              << " kept_host_bytes " << kept_host_bytes << "\n";
+              << " kept_host_bytes " << kept_host_bytes;
+    if (recall_resident)  // appended pairs (the line's readers take pairs); host mode's line is unchanged
+        std::cerr << " recall_resident_seqs " << rr.resident_seqs << " recall_uploaded_seqs " << rr.uploaded_seqs
+                  << " recall_batches " << rr.batches;
+    std::cerr << "\n";
     std::cerr << "all done\n";
     fast_exit(0);  // every output file is closed by now
 }
