@@ -106,6 +106,28 @@ int skm_build_add_batch(skm_build* b, const uint8_t* residues, const uint64_t* s
                         const uint32_t* seq_len, const uint16_t* seq_func, const uint32_t* seq_id,
                         size_t n_seqs);
 
+/* skm_build_add_batch with FastaParser in front of it (fasta_parser.h:38-144 feeding the selection
+ * of signature_build.tcc:84-102 and :93-158), on the device: the files' raw bytes in (bytes /
+ * file_off / n_files as skm_fasta_parse_device takes them, declared below with skm_fasta_table),
+ * the selected records' residues parsed straight into the build's resident buffer -- no host copy of
+ * a residue.  rec_func[r] and rec_id[r] describe parser record r of this call (the records with a
+ * non-empty id, in file order: skm_fasta_table's numbering): rec_func as seq_func (0xFFFF = the
+ * record is not selected, e.g. no kept function or a deleted feature), rec_id as seq_id (may be
+ * NULL, with the same rule).  Staged add_batch residues are flushed first, so add_batch and
+ * add_fasta calls may be mixed and give the sequence order of the calls; works at any world size
+ * (a rank adds its own files).  tab (optional, overwritten; skm_fasta_table_free) gets the table
+ * over every parser record, without residues, for the caller to check against its headers-only
+ * parse.  SKM_E_ARG, with the handle's input as it was before the call (a handle that was prepared
+ * stays prepared, unless the refusal is the record longer than 1,048,575 residues, which is found
+ * after the parse wrote its scratch past the packed residues: the next call prepares again): n_recs differs from the number of
+ * parser records the device finds (the message gives both), a selected rec_func >= n_functions, a
+ * selected record longer than 1,048,575 residues (an unselected one may be), or the argument
+ * errors of skm_fasta_parse_device. */
+struct skm_fasta_table;
+int skm_build_add_fasta(skm_build* b, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                        const uint16_t* rec_func, const uint32_t* rec_id, uint64_t n_recs,
+                        struct skm_fasta_table* tab);
+
 /* Optional capacity hint: the total residues and sequences that will be added, so the HBM
  * residue buffer is allocated once instead of grown.  Batches stream to HBM as they are added,
  * packed into two pinned staging buffers that alternate (the host packs one while the DMA engine
@@ -177,6 +199,8 @@ int skm_build_kernel_timings(skm_build* b, char* names, size_t names_cap, float*
  * is eight parts of its level-2 sub-buckets, or one task when it is grouped unpartitioned), [49]
  * the LDS batches (process_sub calls) they made; both totals over the passes of the run, and both
  * fixed by the input and the pass count, not by the schedule;
+ * [50] device microseconds of skm_build_add_fasta's parses (all calls; the call's host time counts
+ * in [26]);
  * returns entries written. */
 int skm_build_counters(skm_build* b, uint64_t* out, int cap);
 /* Host transport: the rank collectives of a multi-process build run by the caller on host
@@ -278,6 +302,14 @@ int skm_build_debug_overflow(skm_build* b, uint32_t* out, int cap);
  * their span (nwg, span), pass_bits, owner_bits, b1_bits.  The five key-range-pass values
  * (sel_wg .. pf_nwg) are 0 after a one-pass run.  Returns 11, SKM_E_STATE without a completed run. */
 int skm_build_debug_front(skm_build* b, uint64_t* out, int cap);
+/* Diagnostics (read-only, after skm_build_prepare): the resident input as the kernels read it --
+ * *rp = the packed residue bytes (every sequence's residues and a 0 after each), *nseq = the
+ * sequences; res_out (optional, res_cap >= *rp bytes) gets d_res[0, rp), meta_out (optional,
+ * meta_cap >= *nseq records) the sequence table, 16 bytes a sequence: pstart u64, len u32, func
+ * u16, pad u16.  Call it with both NULL for the sizes.  New in this port (the reference keeps its
+ * input in host strings, signature_build.tcc:48-70).  SKM_E_STATE before prepare. */
+int skm_build_debug_input(skm_build* b, uint8_t* res_out, uint64_t res_cap, void* meta_out, uint64_t meta_cap,
+                          uint64_t* rp, uint64_t* nseq);
 /* Diagnostics (read-only, after a run with key-range passes): the staging's exact starts of `pass`,
  * a pass of the run's last emission group: (pf_nwg + 1) rows of 64, row w column d = where staging
  * workgroup w begins in level-0 slice d, row pf_nwg = the slices' ends (at most cap written);

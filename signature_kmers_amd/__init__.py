@@ -133,6 +133,9 @@ _SIGS = {
     "skm_device_mem_info": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "skm_build_create": (C.c_int, [C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.POINTER(_BuildOpts)]),
     "skm_build_add_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t]),
+    "skm_build_add_fasta": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, C.c_uint64, C.POINTER(_FastaTable)]),
+    "skm_build_debug_input": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64)]),
     "skm_build_prepare": (C.c_int, [_P]),
     "skm_build_run": (C.c_int, [_P]),
     "skm_build_last_timings": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
@@ -352,6 +355,9 @@ class _KeptOwner:
             pass
 
 
+SEQ_META_DTYPE = np.dtype([("pstart", np.uint64), ("len", np.uint32), ("func", np.uint16), ("pad", np.uint16)])
+
+
 class SignatureBuilder:
     """Device signature build (SignatureBuilder<8>::extract_kmers + process_kmers).
 
@@ -382,6 +388,36 @@ class SignatureBuilder:
         sid = None if seq_id is None else np.ascontiguousarray(seq_id, dtype=np.uint32)
         _check(lib().skm_build_add_batch(self._h, _ptr(residues), _ptr(seq_off), _ptr(seq_len), _ptr(seq_func),
                                          _ptr(sid) if sid is not None else None, n))
+
+    def add_fasta(self, blobs, rec_func, rec_id=None) -> "FastaTable":
+        """skm_build_add_fasta: add_batch with FastaParser in front of it, on the device.  blobs are
+        the files' raw bytes (as _fasta_input takes them); rec_func[r] / rec_id[r] describe parser
+        record r (the records with a non-empty id, in file order), 0xFFFF = not selected.  The
+        selected records' residues go straight into the build's resident buffer.  Returns the
+        FastaTable over every parser record (without residues)."""
+        data, off = _fasta_input(blobs)
+        rec_func = np.ascontiguousarray(rec_func, dtype=np.uint16)
+        sid = None if rec_id is None else np.ascontiguousarray(rec_id, dtype=np.uint32)
+        if sid is not None and len(sid) != len(rec_func):
+            raise SkmError("rec_id and rec_func differ in length")
+        t = _FastaTable()
+        _check(lib().skm_build_add_fasta(self._h, _ptr(data), _ptr(off), len(off) - 1, _ptr(rec_func),
+                                         _ptr(sid) if sid is not None else None, len(rec_func), C.byref(t)))
+        try:
+            return FastaTable(t)
+        finally:
+            lib().skm_fasta_table_free(C.byref(t))
+
+    def debug_input(self) -> tuple:
+        """skm_build_debug_input (after prepare): (the packed residues d_res[0, rp) as u8, the
+        sequence table as a structured array with pstart u64, len u32, func u16, pad u16)."""
+        rp, nseq = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().skm_build_debug_input(self._h, None, 0, None, 0, C.byref(rp), C.byref(nseq)))
+        res = np.zeros(max(int(rp.value), 1), np.uint8)
+        meta = np.zeros(max(int(nseq.value), 1), SEQ_META_DTYPE)
+        _check(lib().skm_build_debug_input(self._h, _ptr(res), len(res), _ptr(meta), len(meta), C.byref(rp),
+                                           C.byref(nseq)))
+        return res[:int(rp.value)], meta[:int(nseq.value)]
 
     def reserve(self, n_residues: int, n_seqs: int):
         """skm_build_reserve: capacity hint so the HBM residue buffer is allocated once (batches
@@ -438,8 +474,8 @@ class SignatureBuilder:
         return self.counters()["passes"]
 
     def counters(self) -> dict:
-        v = (C.c_uint64 * 50)()
-        n = lib().skm_build_counters(self._h, v, 50)
+        v = (C.c_uint64 * 51)()
+        n = lib().skm_build_counters(self._h, v, 51)
         names = ["windows", "kept", "overflow_subbuckets", "chain_jobs", "chain_samples", "sequences", "grouped",
                  "overflow_elements", "overflow_kept", "big_groups", "big_kept", "passes", "valid", "giant_chains",
                  "giant_max", "redone", "cap_overflow_scratch", "cap_split", "cap_long_samples", "cap_long_jobs",
@@ -449,7 +485,7 @@ class SignatureBuilder:
                  "finish_chunks", "finish_select_dev_us", "finish_sort_dev_us", "finish_gather_dev_us",
                  "finish_d2h_dev_us", "finish_max_chunk", "finish_wide_index", "kept_cap",
                  "free_after_prepare", "recs_rot", "overflow_light_subbuckets", "overflow_light_elements",
-                 "groupby_tasks", "groupby_batches"]
+                 "groupby_tasks", "groupby_batches", "add_fasta_us"]
         return {names[i]: int(v[i]) for i in range(n)}
 
     def debug_jobs(self, k: int = 64) -> list:

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "skm_common.h"
+#include "skm_fasta.h"
 #include "skm_keptdb.h"
 #include "skm_mphdb.h"
 #include "skm_pool.h"
@@ -5401,6 +5402,11 @@ struct skm_build {
     // host seconds in add_batch (all calls), and prepare's phases: the residue / metadata upload, the
     // pass plan (the pass tallies and the routing sketch: device work), the allocations and the rest
     double add_s = 0, add_pack_s = 0, add_wait_s = 0, prep_upload_s = 0, prep_plan_s = 0, prep_rest_s = 0;
+    // skm_build_add_fasta: the device parser's work buffers (they only grow; release_work frees them),
+    // the selected records' packed starts of the last call, and the parse's device seconds (all calls)
+    FastaWork fa;
+    std::vector<uint64_t> fa_sps;
+    double add_fasta_s = 0;
     uint64_t n_windows = 0;
     bool seqid_strict = true;
     bool prepared = false, ran = false;
@@ -7653,6 +7659,83 @@ int skm_build_add_batch(skm_build* b, const uint8_t* residues, const uint64_t* s
     SKM_API_END
 }
 
+int skm_build_add_fasta(skm_build* b, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                        const uint16_t* rec_func, const uint32_t* rec_id, uint64_t n_recs, skm_fasta_table* tab) {
+    SKM_API_BEGIN
+    SKM_CHECK(b, SKM_E_ARG, "null build");
+    if (tab) std::memset(tab, 0, sizeof(*tab));
+    SKM_CHECK(n_recs == 0 || rec_func, SKM_E_ARG, "null rec_func");
+    fasta_check_args(bytes, file_off, n_files);
+    check_not_released(Ranks{b});
+    SKM_HIP(hipSetDevice(b->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t n_sel = 0;
+    for (uint64_t r = 0; r < n_recs; ++r) {
+        if (rec_func[r] == SKM_UNDEFINED_FUNCTION) continue;
+        SKM_CHECK(rec_func[r] < b->opts.n_functions, SKM_E_ARG, "rec_func out of range");
+        ++n_sel;
+    }
+    // what add_batch staged so far goes first: the calls' sequences keep the order of the calls
+    stage_flush(b);
+    skm_fasta_table t{};
+    const FastaSelect T = fasta_parse_select(
+        b->fa, bytes, file_off, n_files, rec_func, n_recs, b->stream,
+        [b](uint64_t sel_bytes) {
+            // from here on the parse writes past rp_total, over prepare's window-load padding: a call
+            // refused after this point (a selected record too long) leaves the handle to be prepared
+            // again; one refused before it (the arguments, the record count) leaves it prepared
+            b->prepared = false;
+            b->ran = false;
+            res_reserve(b, b->rp_total + sel_bytes + 64);
+            return b->d_res.as<uint8_t>() + b->rp_total;
+        },
+        b->fa_sps, &t);
+    b->add_fasta_s += 1e-3 * T.ms;
+    try {
+        SKM_CHECK(T.n_sel == n_sel, SKM_E_HIP, "the device parse selected another number of records than rec_func does");
+        // the selected records: validated, then appended as add_batch appends them
+        uint64_t cum = 0;
+        for (uint64_t r = 0; r < n_recs; ++r) {
+            if (rec_func[r] == SKM_UNDEFINED_FUNCTION) continue;
+            SKM_CHECK(t.seq_len[r] < (1u << ELEM_I_BITS), SKM_E_ARG, "protein longer than 1,048,575 residues");
+            SKM_CHECK(b->fa_sps[r] == cum, SKM_E_HIP, "the device parse packed a selected record at another offset");
+            cum += (uint64_t)t.seq_len[r] + 1;
+        }
+        SKM_CHECK(cum == T.sel_bytes, SKM_E_HIP, "the device parse packed another number of bytes than the table gives");
+        if (b->h_meta.capacity() < b->h_meta.size() + n_sel) {
+            b->h_meta.reserve(std::max(b->h_meta.size() + n_sel, 2 * b->h_meta.capacity()));
+            b->h_seqid.reserve(std::max(b->h_seqid.size() + n_sel, 2 * b->h_seqid.capacity()));
+        }
+        if (T.sel_bytes)  // the 0 after the batch's last selected record
+            SKM_HIP(hipMemsetAsync(b->d_res.as<uint8_t>() + b->rp_total + T.sel_bytes - 1, 0, 1, b->stream));
+        const size_t m0 = b->h_meta.size();
+        size_t k = 0;
+        uint32_t prev = 0;
+        uint64_t nwin = 0;
+        for (uint64_t r = 0; r < n_recs; ++r) {
+            if (rec_func[r] == SKM_UNDEFINED_FUNCTION) continue;
+            const uint32_t sid = rec_id ? rec_id[r] : (uint32_t)(m0 + k);
+            if (k == 0 ? (m0 && sid <= b->h_seqid[m0 - 1]) : (rec_id && sid <= prev)) b->seqid_strict = false;
+            prev = sid;
+            b->h_meta.push_back(SeqMeta{b->rp_total + b->fa_sps[r], t.seq_len[r], rec_func[r], 0});
+            b->h_seqid.push_back(sid);
+            if (t.seq_len[r] >= 8) nwin += t.seq_len[r] - 7;
+            ++k;
+        }
+        b->n_windows += nwin;
+        b->rp_total += T.sel_bytes;
+        b->rp_dev = b->rp_total;
+    } catch (...) {
+        skm_fasta_table_free(&t);
+        throw;
+    }
+    if (tab) *tab = t; else skm_fasta_table_free(&t);
+    b->prepared = false;
+    b->ran = false;
+    b->add_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    SKM_API_END
+}
+
 int skm_build_reserve(skm_build* b, uint64_t n_residues, uint64_t n_seqs) {
     SKM_API_BEGIN
     SKM_CHECK(b, SKM_E_ARG, "null build");
@@ -8009,6 +8092,29 @@ int skm_build_debug_front(skm_build* b, uint64_t* out, int cap) {
     return 11;
 }
 
+// Diagnostics: the resident input after prepare -- the packed residues d_res[0, rp) and the SeqMeta
+// table (16 bytes a sequence: pstart u64, len u32, func u16, pad u16); *rp and *nseq always, the
+// arrays when given and large enough.
+int skm_build_debug_input(skm_build* b, uint8_t* res_out, uint64_t res_cap, void* meta_out, uint64_t meta_cap, uint64_t* rp,
+                          uint64_t* nseq) {
+    SKM_API_BEGIN
+    SKM_CHECK(b && rp && nseq, SKM_E_ARG, "null argument");
+    SKM_CHECK(b->prepared && !b->seqs_released, SKM_E_STATE, "skm_build_debug_input needs a prepared build");
+    *rp = b->rp;
+    *nseq = b->nseq;
+    SKM_HIP(hipSetDevice(b->device));
+    SKM_HIP(hipStreamSynchronize(b->stream));
+    if (res_out) {
+        SKM_CHECK(res_cap >= b->rp, SKM_E_ARG, "res_cap is smaller than the packed residues");
+        if (b->rp) SKM_HIP(hipMemcpy(res_out, b->d_res.p, b->rp, hipMemcpyDeviceToHost));
+    }
+    if (meta_out) {
+        SKM_CHECK(meta_cap >= b->nseq, SKM_E_ARG, "meta_cap is smaller than the sequence count");
+        if (b->nseq) SKM_HIP(hipMemcpy(meta_out, b->d_meta.p, sizeof(SeqMeta) * b->nseq, hipMemcpyDeviceToHost));
+    }
+    SKM_API_END
+}
+
 // Diagnostics: the staging's exact starts of a key-range pass of the last run's LAST emission group
 // (k_pass_starts' wstart: row w, column d = where staging workgroup w begins in level-0 slice d; row
 // pf_nwg = the slices' ends; the earlier groups' copies are overwritten by then); returns the value
@@ -8127,7 +8233,7 @@ int skm_debug_div_check(uint64_t nm, uint32_t per, uint64_t* mismatches) {
 int skm_build_counters(skm_build* b, uint64_t* out, int cap) {
     if (!b || !out) return SKM_E_ARG;
     auto us = [](double sec) { return (uint64_t)(sec * 1e6); };
-    const uint64_t v[50] = {b->n_windows, b->n_kept, b->n_overflow, b->n_jobs, b->n_lens, b->nseq, b->n_local,
+    const uint64_t v[51] = {b->n_windows, b->n_kept, b->n_overflow, b->n_jobs, b->n_lens, b->nseq, b->n_local,
                             b->ovf_elems, b->ovf_kept, b->n_big, b->big_kept, 1ull << b->pass_bits, b->valid_total,
                             b->giant_jobs, b->giant_max, b->n_redo, b->tot_cap, b->split_cap, b->long_cap,
                             b->long_jobs_cap, b->demand[0], b->demand[1], b->demand[2], b->demand[3],
@@ -8139,8 +8245,8 @@ int skm_build_counters(skm_build* b, uint64_t* out, int cap) {
                             (uint64_t)(1e3 * b->handoff.d2h_ms), b->handoff.max_chunk,
                             (uint64_t)b->handoff.wide_index, b->kept_cap, b->free_after_prepare,
                             0ull /* [45] reserved */, b->ovf_light_sub, b->ovf_light_elems, b->bpk_tasks,
-                            b->bpk_batches};
-    int n = std::min(cap, 50);
+                            b->bpk_batches, us(b->add_fasta_s)};
+    int n = std::min(cap, 51);
     for (int i = 0; i < n; ++i) out[i] = v[i];
     return n;
 }
@@ -8444,7 +8550,8 @@ static void release_work(skm_build* b, int level) {
         &b->d_seg_start, &b->d_seg_len, &b->d_vstart, &b->d_xs, &b->d_hv_keys, &b->d_hv_rec, &b->d_hv_len, &b->d_hv_s0,
         &b->d_hv_s1, &b->d_sub_tab, &b->d_jobs2, &b->d_jobs3, &b->d_ids, &b->d_bloom, &b->d_posg, &b->d_histg,
         &b->d_npos, &b->d_selrows, &b->d_seloff, &b->d_gstat, &b->d_long_arena, &b->d_long_jobs, &b->d_ovf2, &b->d_plan,
-        &b->d_run};
+        &b->d_run, &b->fa.d_raw, &b->fa.d_foff, &b->fa.d_tmap, &b->fa.d_tcnt, &b->fa.d_pstart, &b->fa.d_nwin, &b->fa.d_tab,
+        &b->fa.d_rfunc, &b->fa.d_tsel, &b->fa.scan.tiles, &b->fa.scan.total};
     for (DevBuf* d : work) d->release();
     for (ChainSet* cs : {&b->cs_main, &b->cs_ovf, &b->cs_ovf3})
         for (DevBuf* d : {&cs->hist, &cs->offs, &cs->sorted, &cs->long_off}) d->release();

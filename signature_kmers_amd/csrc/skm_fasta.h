@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
+#include <vector>
 
 #include "skm_lookup.h"
 #include "skm_util.h"
@@ -25,6 +27,8 @@ struct FastaWork {
     DevBuf d_pstart;  // per kept record: its packed start
     DevBuf d_nwin;    // per kept record: max(len - 7, 0)
     DevBuf d_tab;     // the download: error flag, file_rec, hdr_pos, seq_len
+    DevBuf d_rfunc;   // fasta_parse_select: rec_func [n_recs]
+    DevBuf d_tsel;    //   per tile: (selected residues, selected records), then their exclusive sums; + totals
     Scanner scan;
     hipEvent_t ev[4] = {};
     ~FastaWork();
@@ -45,5 +49,25 @@ void fasta_check_args(const uint8_t* bytes, const uint64_t* file_off, size_t n_f
 // the stream idle.
 FastaTotals fasta_parse(FastaWork& w, const uint8_t* bytes, const uint64_t* file_off, size_t n_files, hipStream_t st,
                         DevBuf& d_res, DevBuf& d_meta, DevBuf& d_scr_off, int want_residues, skm_fasta_table* tab);
+
+struct FastaSelect {
+    uint64_t n_recs = 0, n_residues = 0;               // every parser record (non-empty id)
+    uint64_t n_sel = 0, sel_residues = 0, sel_bytes = 0;  // the selected ones; sel_bytes = residues + one 0 each
+    float ms = 0;
+};
+
+// The selecting parse (the build's input: FastaParser feeding the selection of
+// signature_build.tcc:93-158).  rec_func[r] describes parser record r (a record with a non-empty id,
+// in file order); 0xFFFF = not selected.  SKM_E_ARG when the bytes hold another number of parser
+// records than n_recs (nothing is written then).  reserve(sel_bytes) is called once the selected
+// size is known (not when it is 0) and returns where the selected records go: their residues and a 0
+// after each, back to back, at any byte address; at most sel_bytes - 1 bytes are written -- the 0 after
+// the last selected record is the caller's.  sel_pstart[r] = the packed start of record r relative
+// to that address (~0 when r is not selected); *tab = fasta_parse's table over every parser record,
+// without residues (the caller frees it).  Returns with the stream idle.
+FastaSelect fasta_parse_select(FastaWork& w, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                               const uint16_t* rec_func, uint64_t n_recs, hipStream_t st,
+                               const std::function<uint8_t*(uint64_t)>& reserve, std::vector<uint64_t>& sel_pstart,
+                               skm_fasta_table* tab);
 
 }  // namespace skm

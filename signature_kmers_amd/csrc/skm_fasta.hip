@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace skm {
@@ -417,6 +418,201 @@ __global__ void k_fasta_meta(const uint64_t* __restrict__ pstart, uint64_t n_rec
     nwin[s] = len >= 8 ? (uint32_t)len - 7 : 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// The selecting parse (fasta_parse_select): the build's input is a selection of each file's records
+// (signature_build.tcc:93-158), rec_func[r] != 0xFFFF of parser record r.  The record current at byte
+// p is S(p) - 1, known from the all-record scan above, so the selection needs one more counting pass
+// and one more sum scan:
+//   k_fasta_sel_count  per tile: selected residues and selected record starts
+//   k_fasta_sum_scan   their exclusive sums and totals
+//   k_fasta_sel_emit   k_fasta_emit with R and S counted over selected events only (the output), and
+//                      over all events for the table (file_rec, hdr_pos, the all-record packed starts
+//                      the lengths come from)
+//   k_fasta_sel_len    per parser record: its length
+// ------------------------------------------------------------------------------------------
+
+// the thread's 16 bytes from state s: on_file(f) for every file that starts at one of them,
+// on_byte(p, c, res, start) for every byte (fasta_step's events)
+template <class FileFn, class ByteFn>
+__device__ __forceinline__ void thread_walk(const uint4& v, uint64_t b, uint32_t s, const uint64_t* __restrict__ file_off,
+                                            uint64_t f, uint64_t fhi, uint64_t nxt, FileFn on_file, ByteFn on_byte) {
+#pragma unroll
+    for (int j = 0; j < (int)FA_BYTES; ++j) {
+        const uint64_t p = b + j;
+        if (p == nxt) {
+            s = F_START;
+            do {
+                on_file(f);
+                ++f;
+                nxt = f < fhi ? file_off[f] : ~0ull;
+            } while (nxt == p);
+        }
+        const uint32_t c = byte_of(v, j);
+        bool r, st;
+        s = fasta_step(s, c, r, st);
+        on_byte(p, c, r, st);
+    }
+}
+
+// Workgroup exclusive sum of a packed pair of counts (low | high << 16, each at most FA_TILE over
+// the workgroup); tot = the workgroup's sum.  s_c holds FA_THREADS / 64 + 1 words.
+__device__ __forceinline__ uint32_t block_excl_pair(uint32_t cnt, uint32_t* s_c, uint32_t& tot) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t x = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    __syncthreads();  // s_c may still be read from an earlier call
+    if (lane == 63) s_c[wave] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t acc = 0;
+        for (int w = 0; w < (int)FA_THREADS / 64; ++w) {
+            const uint32_t t = s_c[w];
+            s_c[w] = acc;
+            acc += t;
+        }
+        s_c[FA_THREADS / 64] = acc;
+    }
+    __syncthreads();
+    tot = s_c[FA_THREADS / 64];
+    return s_c[wave] + x - cnt;
+}
+
+__device__ __forceinline__ bool rec_selected(const uint16_t* __restrict__ rec_func, uint64_t n_recs, uint64_t r) {
+    return r < n_recs && rec_func[r] != 0xFFFFu;
+}
+
+// the thread's selected residues | selected record starts << 16, S = the record starts before its
+// first byte
+__device__ __forceinline__ uint32_t thread_sel_counts(const uint4& v, uint64_t b, uint32_t s0,
+                                                      const uint64_t* __restrict__ file_off, uint64_t f0, uint64_t fhi,
+                                                      uint64_t nxt0, const uint16_t* __restrict__ rec_func, uint64_t n_recs,
+                                                      uint64_t S) {
+    bool cur = S > 0 && rec_selected(rec_func, n_recs, S - 1);
+    uint32_t sel = 0;
+    thread_walk(v, b, s0, file_off, f0, fhi, nxt0, [](uint64_t) {},
+                [&](uint64_t, uint32_t, bool r, bool st) {
+                    if (r && cur) ++sel;
+                    if (st) {
+                        cur = rec_selected(rec_func, n_recs, S);
+                        if (cur) sel += 0x10000u;
+                        ++S;
+                    }
+                });
+    return sel;
+}
+
+__global__ __launch_bounds__(FA_THREADS) void k_fasta_sel_count(const uint8_t* __restrict__ raw, uint64_t n,
+                                                                const uint64_t* __restrict__ file_off, uint64_t n_files,
+                                                                const uint64_t* __restrict__ tile_state,
+                                                                const uint64_t* __restrict__ tile_cnt,
+                                                                const uint16_t* __restrict__ rec_func, uint64_t n_recs,
+                                                                uint64_t* __restrict__ tile_sel) {
+    __shared__ uint64_t s_f[2], s_w[FA_THREADS / 64 + 1];
+    __shared__ uint32_t s_c[FA_THREADS / 64 + 1];
+    const uint64_t t0 = (uint64_t)blockIdx.x * FA_TILE, b = t0 + (uint64_t)threadIdx.x * FA_BYTES;
+    const uint4 v = *reinterpret_cast<const uint4*>(raw + b);
+    uint64_t fhi, nxt;
+    const uint64_t f0 = thread_first_file(file_off, n_files, n, t0, b, s_f, fhi, nxt);
+    const uint64_t nxt0 = nxt;
+    const uint64_t e = block_excl_map(thread_map(v, b, file_off, f0, fhi, nxt), s_w);
+    const uint32_t s0 = map_apply(e, (uint32_t)tile_state[blockIdx.x]);
+    uint32_t cnt = 0;
+    thread_walk(v, b, s0, file_off, f0, fhi, nxt0, [](uint64_t) {},
+                [&](uint64_t, uint32_t, bool r, bool st) { cnt += (r ? 1u : 0u) + (st ? 0x10000u : 0u); });
+    uint32_t tot;
+    const uint32_t ex = block_excl_pair(cnt, s_c, tot);
+    (void)tot;
+    const uint64_t S = tile_cnt[2 * (uint64_t)blockIdx.x + 1] + (ex >> 16);
+    const uint32_t sel = thread_sel_counts(v, b, s0, file_off, f0, fhi, nxt0, rec_func, n_recs, S);
+    uint32_t stot;
+    (void)block_excl_pair(sel, s_c, stot);
+    if (threadIdx.x == 0) {
+        tile_sel[2 * (uint64_t)blockIdx.x] = stot & 0xFFFFu;
+        tile_sel[2 * (uint64_t)blockIdx.x + 1] = stot >> 16;
+    }
+}
+
+// k_fasta_emit's invariant with R and S counted over selected events only (Rs, Ss): a selected residue
+// at p goes to dst[Rs(p) + Ss(p) - 1] and a selected record start puts the 0 that ends the selected
+// record before it at the same expression, its own residues starting at sel_pstart = Rs + Ss.  The
+// first selected start of all has position -1 (not stored); the 0 after the last selected record is
+// the host's.  dst is any byte address: the range is stored byte by byte, contiguous over the
+// workgroup.  all_pstart, hdr_pos and file_rec are k_fasta_emit's, over every parser record.
+__global__ __launch_bounds__(FA_THREADS) void k_fasta_sel_emit(
+    const uint8_t* __restrict__ raw, uint64_t n, const uint64_t* __restrict__ file_off, uint64_t n_files,
+    const uint64_t* __restrict__ tile_state, const uint64_t* __restrict__ tile_cnt, const uint64_t* __restrict__ tile_sel,
+    const uint16_t* __restrict__ rec_func, uint64_t n_recs, uint8_t* __restrict__ dst, uint64_t sel_bytes,
+    uint64_t* __restrict__ sel_pstart, uint64_t* __restrict__ all_pstart, uint64_t* __restrict__ hdr_pos,
+    uint64_t* __restrict__ file_rec) {
+    __shared__ uint64_t s_f[2], s_w[FA_THREADS / 64 + 1];
+    __shared__ uint32_t s_c[FA_THREADS / 64 + 1];
+    __shared__ uint8_t s_out[FA_TILE];
+    const uint64_t t0 = (uint64_t)blockIdx.x * FA_TILE, b = t0 + (uint64_t)threadIdx.x * FA_BYTES;
+    const uint4 v = *reinterpret_cast<const uint4*>(raw + b);
+    uint64_t fhi, nxt;
+    const uint64_t f0 = thread_first_file(file_off, n_files, n, t0, b, s_f, fhi, nxt);
+    const uint64_t nxt0 = nxt;
+    const uint64_t e = block_excl_map(thread_map(v, b, file_off, f0, fhi, nxt), s_w);
+    const uint32_t s0 = map_apply(e, (uint32_t)tile_state[blockIdx.x]);
+    uint32_t cnt = 0;
+    thread_walk(v, b, s0, file_off, f0, fhi, nxt0, [](uint64_t) {},
+                [&](uint64_t, uint32_t, bool r, bool st) { cnt += (r ? 1u : 0u) + (st ? 0x10000u : 0u); });
+    uint32_t tot, stot;
+    const uint32_t ex = block_excl_pair(cnt, s_c, tot);
+    (void)tot;
+    uint64_t R = tile_cnt[2 * (uint64_t)blockIdx.x] + (ex & 0xFFFFu), S = tile_cnt[2 * (uint64_t)blockIdx.x + 1] + (ex >> 16);
+    const uint32_t sel = thread_sel_counts(v, b, s0, file_off, f0, fhi, nxt0, rec_func, n_recs, S);
+    const uint32_t sex = block_excl_pair(sel, s_c, stot);
+    const uint64_t o0 = tile_sel[2 * (uint64_t)blockIdx.x] + tile_sel[2 * (uint64_t)blockIdx.x + 1];
+    uint32_t k = (sex & 0xFFFFu) + (sex >> 16);  // the thread's first selected event in the tile's output
+    bool cur = S > 0 && rec_selected(rec_func, n_recs, S - 1);
+    thread_walk(
+        v, b, s0, file_off, f0, fhi, nxt0, [&](uint64_t f) { file_rec[f] = S; },
+        [&](uint64_t p, uint32_t c, bool r, bool st) {
+            // (as in k_fasta_emit: the bounds hold by construction and are checked all the same)
+            if (r) {
+                if (cur) {
+                    if (k < FA_TILE) s_out[k] = (uint8_t)c;
+                    ++k;
+                }
+                ++R;
+            }
+            if (st) {
+                cur = rec_selected(rec_func, n_recs, S);
+                if (cur) {
+                    if (k < FA_TILE) s_out[k] = 0;
+                    ++k;
+                }
+                if (S < n_recs) {
+                    all_pstart[S] = R + S;
+                    sel_pstart[S] = cur ? o0 + k - 1 : ~0ull;  // its start is event o0 + k - 1, stored one before
+                    uint64_t q = p - 1;  // the '>' that opened the record: only '\r' can lie between
+                    while (q > 0 && raw[q] == '\r') --q;
+                    hdr_pos[S] = q;
+                }
+                ++S;
+            }
+        });
+    __syncthreads();
+    const uint32_t nev = min((stot & 0xFFFFu) + (stot >> 16), FA_TILE);
+    for (uint32_t i = threadIdx.x; i < nev; i += FA_THREADS)
+        if (o0 + i && o0 + i < sel_bytes) dst[o0 + i - 1] = s_out[i];
+}
+
+// per parser record its length; *err |= 1 when one is too long for u32
+__global__ void k_fasta_sel_len(const uint64_t* __restrict__ all_pstart, uint64_t n_recs, uint64_t rp,
+                                uint32_t* __restrict__ seq_len, uint64_t* __restrict__ err) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_recs) return;
+    const uint64_t len = (s + 1 < n_recs ? all_pstart[s + 1] : rp) - all_pstart[s] - 1;
+    if (len > 0xFFFFFFFEull) *err = 1;
+    seq_len[s] = (uint32_t)len;
+}
+
 }  // namespace
 
 FastaWork::~FastaWork() {
@@ -538,6 +734,112 @@ FastaTotals fasta_parse(FastaWork& w, const uint8_t* bytes, const uint64_t* file
         }
         *tab = t;
     }
+    return T;
+}
+
+FastaSelect fasta_parse_select(FastaWork& w, const uint8_t* bytes, const uint64_t* file_off, size_t n_files,
+                               const uint16_t* rec_func, uint64_t n_recs, hipStream_t st,
+                               const std::function<uint8_t*(uint64_t)>& reserve, std::vector<uint64_t>& sel_pstart,
+                               skm_fasta_table* tab) {
+    FastaSelect T;
+    const uint64_t n = file_off[n_files];
+    const uint64_t nt = ceil_div(n, FA_TILE), n_pad = nt * FA_TILE;
+    for (auto& e : w.ev)
+        if (!e) SKM_HIP(hipEventCreate(&e));
+    uint64_t tot[4] = {0, 0, 0, 0};  // residues, records; selected residues, selected records
+    float ms0 = 0, ms1 = 0;
+    if (n) {
+        alloc_reported(w.d_raw, n_pad, "FASTA file bytes");
+        w.d_foff.ensure(8 * (n_files + 1));
+        w.d_tmap.ensure(8 * nt);
+        w.d_tcnt.ensure(16 * (nt + 1));
+        w.d_tsel.ensure(16 * (nt + 1));
+        w.d_rfunc.ensure(2 * std::max<uint64_t>(n_recs, 1));
+        SKM_HIP(hipMemcpyAsync(w.d_raw.p, bytes, n, hipMemcpyHostToDevice, st));
+        if (n_pad > n) SKM_HIP(hipMemsetAsync(w.d_raw.as<uint8_t>() + n, '\r', n_pad - n, st));
+        SKM_HIP(hipMemcpyAsync(w.d_foff.p, file_off, 8 * (n_files + 1), hipMemcpyHostToDevice, st));
+        if (n_recs) SKM_HIP(hipMemcpyAsync(w.d_rfunc.p, rec_func, 2 * n_recs, hipMemcpyHostToDevice, st));
+        SKM_HIP(hipEventRecord(w.ev[0], st));
+        hipLaunchKernelGGL(k_fasta_maps, dim3((uint32_t)nt), dim3(FA_THREADS), 0, st, w.d_raw.as<uint8_t>(), n,
+                           w.d_foff.as<uint64_t>(), (uint64_t)n_files, w.d_tmap.as<uint64_t>());
+        hipLaunchKernelGGL(k_fasta_map_scan, dim3(1), dim3(1024), 0, st, w.d_tmap.as<uint64_t>(), nt);
+        hipLaunchKernelGGL(k_fasta_count, dim3((uint32_t)nt), dim3(FA_THREADS), 0, st, w.d_raw.as<uint8_t>(), n,
+                           w.d_foff.as<uint64_t>(), (uint64_t)n_files, w.d_tmap.as<uint64_t>(), w.d_tcnt.as<uint64_t>());
+        hipLaunchKernelGGL(k_fasta_sum_scan, dim3(1), dim3(1024), 0, st, w.d_tcnt.as<uint64_t>(), nt);
+        // a record past the caller's n_recs counts as not selected: the counts are compared below,
+        // before anything is made of the selection
+        hipLaunchKernelGGL(k_fasta_sel_count, dim3((uint32_t)nt), dim3(FA_THREADS), 0, st, w.d_raw.as<uint8_t>(), n,
+                           w.d_foff.as<uint64_t>(), (uint64_t)n_files, w.d_tmap.as<uint64_t>(), w.d_tcnt.as<uint64_t>(),
+                           w.d_rfunc.as<uint16_t>(), n_recs, w.d_tsel.as<uint64_t>());
+        hipLaunchKernelGGL(k_fasta_sum_scan, dim3(1), dim3(1024), 0, st, w.d_tsel.as<uint64_t>(), nt);
+        SKM_HIP(hipGetLastError());
+        SKM_HIP(hipEventRecord(w.ev[1], st));
+        SKM_HIP(hipMemcpyAsync(tot, w.d_tcnt.as<uint64_t>() + 2 * nt, 16, hipMemcpyDeviceToHost, st));
+        SKM_HIP(hipMemcpyAsync(tot + 2, w.d_tsel.as<uint64_t>() + 2 * nt, 16, hipMemcpyDeviceToHost, st));
+        SKM_HIP(hipStreamSynchronize(st));
+        SKM_HIP(hipEventElapsedTime(&ms0, w.ev[0], w.ev[1]));
+    }
+    T.ms = ms0;
+    SKM_CHECK(tot[1] == n_recs, SKM_E_ARG,
+              "the files hold " + std::to_string(tot[1]) + " records with an id, the selection describes " +
+                  std::to_string(n_recs));
+    T.n_recs = n_recs;
+    T.n_residues = tot[0];
+    T.sel_residues = tot[2];
+    T.n_sel = tot[3];
+    T.sel_bytes = tot[2] + tot[3];
+    const uint64_t rp_all = tot[0] + n_recs;
+    uint8_t* dst = T.sel_bytes ? reserve(T.sel_bytes) : nullptr;
+    // the download: error flag, file_rec [n_files + 1], hdr_pos [n_recs], sel_pstart [n_recs], seq_len [n_recs]
+    const uint64_t tab_bytes = 8 * (1 + n_files + 1 + 2 * n_recs) + 4 * n_recs;
+    w.d_tab.ensure(tab_bytes);
+    uint64_t* d_err = w.d_tab.as<uint64_t>();
+    uint64_t* d_file_rec = d_err + 1;
+    uint64_t* d_hdr = d_file_rec + n_files + 1;
+    uint64_t* d_sps = d_hdr + n_recs;
+    uint32_t* d_len = reinterpret_cast<uint32_t*>(d_sps + n_recs);
+    SKM_HIP(hipMemsetAsync(w.d_tab.p, 0, 8 * (1 + n_files + 1), st));
+    if (n) {
+        w.d_pstart.ensure(8 * std::max<uint64_t>(n_recs, 1));
+        SKM_HIP(hipEventRecord(w.ev[2], st));
+        hipLaunchKernelGGL(k_fasta_sel_emit, dim3((uint32_t)nt), dim3(FA_THREADS), 0, st, w.d_raw.as<uint8_t>(), n,
+                           w.d_foff.as<uint64_t>(), (uint64_t)n_files, w.d_tmap.as<uint64_t>(), w.d_tcnt.as<uint64_t>(),
+                           w.d_tsel.as<uint64_t>(), w.d_rfunc.as<uint16_t>(), n_recs, dst, T.sel_bytes, d_sps,
+                           w.d_pstart.as<uint64_t>(), d_hdr, d_file_rec);
+        if (n_recs)
+            hipLaunchKernelGGL(k_fasta_sel_len, dim3((uint32_t)ceil_div(n_recs, 256)), dim3(256), 0, st,
+                               w.d_pstart.as<uint64_t>(), n_recs, rp_all, d_len, d_err);
+        SKM_HIP(hipGetLastError());
+        SKM_HIP(hipEventRecord(w.ev[3], st));
+    }
+    std::vector<uint8_t> host(tab_bytes);
+    SKM_HIP(hipMemcpyAsync(host.data(), w.d_tab.p, tab_bytes, hipMemcpyDeviceToHost, st));
+    SKM_HIP(hipStreamSynchronize(st));
+    if (n) SKM_HIP(hipEventElapsedTime(&ms1, w.ev[2], w.ev[3]));
+    T.ms = ms0 + ms1;
+    const uint64_t* h = reinterpret_cast<const uint64_t*>(host.data());
+    SKM_CHECK(!h[0], SKM_E_ARG, "a record is longer than 2^32 - 2 residues");
+    sel_pstart.assign(h + 1 + n_files + 1 + n_recs, h + 1 + n_files + 1 + 2 * n_recs);
+    std::memset(tab, 0, sizeof(*tab));
+    skm_fasta_table t{};
+    t.n_files = n_files;
+    t.n_recs = n_recs;
+    t.n_residues = T.n_residues;
+    t.parse_ms = T.ms;
+    t.file_rec = (uint64_t*)std::malloc(8 * (n_files + 1));
+    t.seq_len = (uint32_t*)std::malloc(4 * std::max<uint64_t>(n_recs, 1));
+    t.hdr_pos = (uint64_t*)std::malloc(8 * std::max<uint64_t>(n_recs, 1));
+    if (!(t.file_rec && t.seq_len && t.hdr_pos)) {
+        skm_fasta_table_free(&t);
+        throw Error(SKM_E_OOM, "host allocation failed");
+    }
+    std::memcpy(t.file_rec, h + 1, 8 * (n_files + 1));
+    for (size_t f = 0; f <= n_files; ++f)  // the files that start at the end of the bytes, and the end itself
+        if (file_off[f] == n) t.file_rec[f] = n_recs;
+    std::memcpy(t.hdr_pos, h + 1 + n_files + 1, 8 * n_recs);
+    std::memcpy(t.seq_len, h + 1 + n_files + 1 + 2 * n_recs, 4 * n_recs);
+    for (uint64_t r = 0; r < n_recs; ++r) t.n_windows += t.seq_len[r] >= 8 ? t.seq_len[r] - 7 : 0;
+    *tab = t;
     return T;
 }
 

@@ -24,6 +24,13 @@
 // sequences (skm_build_recall) and uploads only the records the selection left out; every output is
 // the same.  The build handle then lives until the recall is done, and keeps its sequences where
 // it releases its work buffers.
+// --fasta-parse host|device: the sequence bodies of the training files are parsed into host strings
+// and packed into the build by host threads, or (device) the host parses headers only and every
+// group of whole files (--fasta-group-mb, default 256) goes to the GPU as raw bytes, where the
+// records the selection names are parsed straight into the build's resident buffer
+// (skm_build_add_fasta).  The records the selection left out are parsed on the host from their byte
+// ranges alone, for the recall (the parse error reports of those ranges, which can hold records with
+// an empty id too, appear a second time on stderr).  Needs one GPU and --recall-source device; every output is the same.
 // Multi-GPU: --n-gpus N forks one process per GPU (rank r on device r) before
 // any GPU or thread use; or, under an external launcher (RANK / WORLD_SIZE / LOCAL_RANK in the
 // environment, e.g. torchrun --no-python), each launched process is one rank and rank 0 hands the
@@ -169,6 +176,123 @@ void dump_extract(const std::string& path, const std::vector<FastaFile>& files, 
     if (!o) die("cannot write " + path);
 }
 
+bool read_whole_file(const std::string& path, std::vector<uint8_t>& buf) {
+    FILE* fp = std::fopen(path.c_str(), "rb");
+    if (!fp) return false;
+    for (;;) {
+        const size_t at = buf.size();
+        buf.resize(at + (4u << 20));
+        const size_t got = std::fread(buf.data() + at, 1, 4u << 20, fp);
+        buf.resize(at + got);
+        if (got < (4u << 20)) break;
+    }
+    const bool ok = !std::ferror(fp);
+    std::fclose(fp);
+    return ok;
+}
+
+// --fasta-parse device: files [f0, f1) into the build in groups of whole files of up to group_bytes,
+// each group one skm_build_add_fasta call over the files' bytes.  files are the headers-only host
+// parses and batches their selections (wait_selected(f) returns once batches[f] is made).  The
+// device's table is checked against the host parse file by file.  The records a selection left out
+// are parsed on the host from their byte ranges (a run's first '>' to the next selected record's, or
+// the file's end): files[f].residues then holds these records' residues alone and off[r] points into it for
+// them -- what call_files_resident reads; host_bytes counts them.
+void add_files_on_device(skm_build* b, std::vector<FastaFile>& files, const std::vector<BuildBatch>& batches, size_t f0,
+                         size_t f1, uint64_t group_bytes, int device, const std::function<void(size_t)>& wait_selected,
+                         uint64_t& host_bytes) {
+    // test hook (tests/test_gpu_cli_build_fasta.py): the device is given one record more in this file
+    const char* extra = std::getenv("SKM_CLI_FASTA_EXTRA_RECORD");
+    std::vector<uint64_t> fsize(f1, 0);
+    for (size_t f = f0; f < f1; ++f) {
+        struct stat sb;
+        if (::stat(files[f].path.c_str(), &sb) == 0) fsize[f] = (uint64_t)sb.st_size;
+    }
+    std::vector<uint8_t> buf;
+    std::vector<uint64_t> foff;
+    std::vector<uint16_t> rfunc;
+    std::vector<uint32_t> rid;
+    for (size_t g0 = f0; g0 < f1;) {
+        size_t g1 = g0;
+        uint64_t bytes = 0;
+        while (g1 < f1 && (g1 == g0 || bytes + fsize[g1] <= group_bytes)) bytes += fsize[g1++];
+        buf.clear();
+        foff.assign(1, 0);
+        rfunc.clear();
+        rid.clear();
+        for (size_t f = g0; f < g1; ++f) {
+            wait_selected(f);
+            if (!read_whole_file(files[f].path, buf)) die("cannot read " + files[f].path);
+            if (extra && (size_t)std::atol(extra) == f) {
+                const char* inj = "\n>injected\n";
+                buf.insert(buf.end(), inj, inj + std::strlen(inj));
+            }
+            foff.push_back(buf.size());
+            const size_t base = rfunc.size();
+            rfunc.resize(base + files[f].size(), (uint16_t)SKM_UNDEFINED_FUNCTION);
+            rid.resize(base + files[f].size(), 0);
+            const BuildBatch& bb = batches[f];
+            for (size_t s = 0; s < bb.rec.size(); ++s) {
+                rfunc[base + bb.rec[s]] = bb.func[s];
+                rid[base + bb.rec[s]] = bb.seq_id[s];
+            }
+        }
+        const size_t nf = g1 - g0;
+        skm_fasta_table tab{};
+        int rc = skm_build_add_fasta(b, buf.data(), foff.data(), nf, rfunc.data(), rid.data(), rfunc.size(), &tab);
+        const std::string add_err = rc ? skm_last_error() : "";
+        // a refused group is parsed without the build, for the table that names the file
+        if (rc == SKM_E_ARG && skm_fasta_parse_device(buf.data(), foff.data(), nf, device, 0, &tab) != SKM_OK) tab = {};
+        if (rc && !tab.file_rec) die("skm_build_add_fasta: " + add_err);
+        for (size_t i = 0; i < nf; ++i) {
+            const FastaFile& F = files[g0 + i];
+            const uint64_t r0 = tab.file_rec[i], n = tab.file_rec[i + 1] - r0;
+            if (n != F.size())
+                die("device FASTA parse of " + F.path + ": " + std::to_string(n) + " records, the host parse has " +
+                    std::to_string(F.size()));
+            for (size_t r = 0; r < F.size(); ++r)
+                if (tab.seq_len[r0 + r] != F.len[r])
+                    die("device FASTA parse of " + F.path + ": record " + F.ids[r] + " has " +
+                        std::to_string(tab.seq_len[r0 + r]) + " residues, the host parse has " + std::to_string(F.len[r]));
+        }
+        if (rc) die("skm_build_add_fasta: " + add_err);
+        for (size_t i = 0; i < nf; ++i) {
+            FastaFile& F = files[g0 + i];
+            const uint64_t r0 = tab.file_rec[i];
+            const std::vector<uint32_t>& rec = batches[g0 + i].rec;
+            // every run of consecutive left-out records in one parse, appended to `lo`
+            FastaFile lo;
+            std::vector<size_t> lo_rec;
+            size_t k = 0;
+            for (size_t r = 0; r < F.size();) {
+                if (k < rec.size() && rec[k] == r) {
+                    ++k;
+                    F.off[r++] = 0;
+                    continue;
+                }
+                size_t e = r;
+                while (e < F.size() && !(k < rec.size() && rec[k] == e)) lo_rec.push_back(e++);
+                const uint64_t a = tab.hdr_pos[r0 + r], z = e < F.size() ? tab.hdr_pos[r0 + e] : foff[i + 1];
+                parse_fasta_buffer((const char*)buf.data() + a, (size_t)(z - a), lo, true);
+                r = e;
+            }
+            if (lo.size() != lo_rec.size())
+                die("host parse of the left-out records of " + F.path + " from their byte ranges: " +
+                    std::to_string(lo.size()) + " records, the selection leaves out " + std::to_string(lo_rec.size()));
+            for (size_t j = 0; j < lo_rec.size(); ++j) {
+                const size_t r = lo_rec[j];
+                if (lo.len[j] != F.len[r] || lo.ids[j] != F.ids[r])
+                    die("host parse of record " + F.ids[r] + " of " + F.path + " from its byte range differs from the file's parse");
+                F.off[r] = lo.off[j];
+                host_bytes += F.len[r];
+            }
+            F.residues = std::move(lo.residues);
+        }
+        skm_fasta_table_free(&tab);
+        g0 = g1;
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -189,7 +313,8 @@ int main(int argc, char** argv) {
                 {"n-gpus", 0, false, false},           {"comm", 0, false, false},
                 {"comm-file", 0, false, false},        {"recall-db", 0, false, false},
                 {"perfect-hash-source", 0, false, false}, {"best-call", 0, false, false},
-                {"final-kmers-source", 0, false, false}, {"recall-source", 0, false, false}};
+                {"final-kmers-source", 0, false, false}, {"recall-source", 0, false, false},
+                {"fasta-parse", 0, false, false},      {"fasta-group-mb", 0, false, false}};
     std::string err;
     if (!op.parse(argc, argv, err)) die(err);
     if (op.has("help")) {
@@ -226,6 +351,12 @@ int main(int argc, char** argv) {
                   << "                                       device: the proteins selected into the build are recalled in place from\n"
                   << "                                       the build's resident sequences, only the others are uploaded, and\n"
                   << "                                       find_best_call runs on the device (one GPU; the outputs are the same)\n"
+                  << "  --fasta-parse arg                    host (default): the sequence bodies are parsed and packed on the host;\n"
+                  << "                                       device: the host parses headers only and the GPU parses the selected\n"
+                  << "                                       records from the files' bytes into the build (one GPU, needs\n"
+                  << "                                       --recall-source device; the outputs are the same)\n"
+                  << "  --fasta-group-mb arg                 --fasta-parse device: whole files per device parse, up to this many MB\n"
+                  << "                                       (default 256; a larger file is a group of its own)\n"
                   << "  -h [ --help ]                        show this help message\n";
         return 1;
     }
@@ -260,6 +391,15 @@ int main(int argc, char** argv) {
     if (recall_source == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1))
         die("--recall-source device needs one GPU: a rank of a multi-rank build holds only its own shard's sequences");
     const bool recall_resident = recall_source == "device";
+    const std::string fasta_parse = op.get("fasta-parse", "host");
+    if (fasta_parse != "host" && fasta_parse != "device") die("--fasta-parse must be host or device");
+    if (fasta_parse == "device" && (launched || std::atoi(op.get("n-gpus", "1").c_str()) > 1 || !recall_resident))
+        die("--fasta-parse device needs one GPU and --recall-source device: the host keeps no training residues to "
+            "upload again for the recall");
+    const bool fasta_dev = fasta_parse == "device" && !op.has("dump-extract");  // the dump stays on the host parse
+    const double fasta_group_mb = std::atof(op.get("fasta-group-mb", "256").c_str());  // fractions are taken too
+    if (!(fasta_group_mb > 0)) die("--fasta-group-mb must be positive");
+    const uint64_t fasta_group_bytes = (uint64_t)std::max(1.0, fasta_group_mb * 1048576.0);
     const int release_level = recall_resident ? 2 : 1;  // 2 keeps the resident sequences for the recall
     // every consumer of the kept set on the device: no host copy of it is made
     const bool kept_on_device = fk_source == "device" && recall_db == "device" &&
@@ -346,7 +486,7 @@ int main(int argc, char** argv) {
     // The FunctionMap needs every file's headers; residues are kept only for the files this rank
     // builds -- and on rank 0, whose recall pass reads every sequence, for all of them.
     std::vector<char> keep_res(all_paths.size(), 0);
-    for (size_t f = 0; f < all_paths.size(); ++f) keep_res[f] = rank == 0 || dump || (f >= f0 && f < f1);
+    for (size_t f = 0; f < all_paths.size(); ++f) keep_res[f] = !fasta_dev && (rank == 0 || dump || (f >= f0 && f < f1));
     double t0 = now_s();
     bool parsed_ok = true;
     std::string parse_err;
@@ -442,7 +582,7 @@ int main(int argc, char** argv) {
     {
         uint64_t nres = 0, nseq = 0;
         for (size_t f = f0; f < f1; ++f) {
-            nres += files[f].residues.size();
+            nres += files[f].n_residues;
             nseq += files[f].size();
         }
         check(skm_build_reserve(b, nres, nseq), "skm_build_reserve");
@@ -466,7 +606,19 @@ int main(int argc, char** argv) {
     }
     const double t_create = now_s() - t_create0;
     const double t_add0 = now_s();
-    for (size_t f = f0; f < f1; ++f) {
+    uint64_t host_residue_bytes = 0;
+    double t_add_fasta = 0;
+    if (fasta_dev) {
+        add_files_on_device(b, files, batches, f0, f1, fasta_group_bytes, device,
+                            [&](size_t f) {
+                                std::unique_lock<std::mutex> g(sel_mu);
+                                sel_cv.wait(g, [&] { return sel_done[f] != 0; });
+                            },
+                            host_residue_bytes);
+        uint64_t ctr[51] = {0};
+        if (skm_build_counters(b, ctr, 51) > 50) t_add_fasta = 1e-6 * (double)ctr[50];
+    }
+    for (size_t f = f0; f < f1 && !fasta_dev; ++f) {
         {
             std::unique_lock<std::mutex> g(sel_mu);
             sel_cv.wait(g, [&] { return sel_done[f] != 0; });
@@ -666,6 +818,7 @@ int main(int argc, char** argv) {
               << t_startup << " defs " << t_defs << " hip_init " << t_hip_init << " create " << t_create
               << " parse_files " << t_files << " fm_load " << t_fm << " recall_deferred " << recall_deferred
               << " kept_host_bytes " << kept_host_bytes;
+    if (fasta_dev) std::cerr << " add_fasta " << t_add_fasta << " host_residue_bytes " << host_residue_bytes;
     if (recall_resident)  // appended pairs (the line's readers take pairs); host mode's line is unchanged
         std::cerr << " recall_resident_seqs " << rr.resident_seqs << " recall_uploaded_seqs " << rr.uploaded_seqs
                   << " recall_batches " << rr.batches;
