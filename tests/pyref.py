@@ -90,6 +90,23 @@ def group_stats(lengths_in_visit_order):
     return d2u16(mean), d2u16(p2.result()), d2u16(var)
 
 
+def ref_chain(xs):
+    """One deferred chain over the samples in visit order: (P^2 median, running variance with the
+    u16-wrapping sum), raw doubles."""
+    p2 = P2()
+    cnt, s, var = 0, 0, 0.0
+    for x in xs:
+        x = int(x)
+        cnt += 1
+        s = (s + x) & 0xFFFF
+        p2.add(x)
+        if cnt > 1:
+            m = s / cnt
+            t = x - m
+            var = var * (cnt - 1) / cnt + t * t / (cnt - 1)
+    return p2.result(), var
+
+
 def f32(x: float) -> float:
     return struct.unpack("<f", struct.pack("<f", x))[0]
 

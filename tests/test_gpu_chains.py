@@ -5,24 +5,9 @@ restatement of Boost.Accumulators (tests/pyref.py), raw doubles bit 
 import numpy as np
 import pytest
 
-import pyref
+from pyref import ref_chain
 
 pytestmark = pytest.mark.gpu
-
-
-def ref_chain(xs):
-    p2 = pyref.P2()
-    cnt, s, var = 0, 0, 0.0
-    for x in xs:
-        x = int(x)
-        cnt += 1
-        s = (s + x) & 0xFFFF
-        p2.add(x)
-        if cnt > 1:
-            m = s / cnt
-            t = x - m
-            var = var * (cnt - 1) / cnt + t * t / (cnt - 1)
-    return p2.result(), var
 
 
 def cases():
